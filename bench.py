@@ -5,17 +5,27 @@ Workload (BASELINE.json configs[1]): 2048-bit key, float32 tensor of 2^20 elemen
 (x = randn*4, seed 20241218+rank, first 8 entries [0,-0,1e-30,-1e-30,3.4e38,-3.4e38,1,-1]),
 already resident in HBM.  One step = fixed-point encode (device) + obfuscated encryption
 (device ChaCha20 r, r^n mod n^2) of the whole batch.  N GPUs = N independent shards (weak
-scaling, one process per GPU, no collective in the timed region).  Also reported (every
-rank; rank 0 prints): decrypt and ct-add throughput on the same data, the end-to-end rate
+scaling, one process per GPU, no collective in the timed region).  A plain run sets up, warms
+up, times the steps and prints the headline line (with the roofline of the timed launches).
+`--dump-outputs DIR` then writes what the last timed step returned: a fixed, seeded sample of
+16,384 ciphertexts (all of them below that size) in the reference's signed form, as
+DIR/ciphertext_magnitude.npy (float64 [S, 128]: the uint32 words, least significant first),
+ciphertext_negative.npy and ciphertext_exp.npy (float32 [S]); rank r > 0 writes
+<name>.rank<r>.npy.  With it the obfuscation is drawn from a fixed ChaCha20 key and nonce
+sequence, so the same arguments give the same ciphertexts in every run and build.
+
+`--full` also reports (every rank; rank 0 prints), after the headline and in the same line:
+decrypt and ct-add throughput on the same data, the end-to-end rate
 with host->device and device->host copies, a decrypt round-trip check, key-holder (CRT)
 encryption, ct x pt, the SecureBoost histogram (unpacked and gh-packed), the Hetero-LR
 gradient step, for N>1 the ciphertext all-gather and the cross-rank histogram fold, the
-roofline of the dominant kernel and, at N=1, the CPU baseline (libgmp port of the
+rooflines of those kernels and, at N=1, the CPU baseline (libgmp port of the
 reference call sequence).  `config5` is BASELINE config 5 in weak form: 12.5M elements per
 rank (100M at 8 GPUs), then the gather to rank 0 and the all-gather.  Progress goes to
 stderr, one line per leg; the JSON line is the only stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ELEMENTS] [--config5-per-rank M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ELEMENTS] [--dump-outputs DIR]
+                    [--full [--config5-per-rank M] [--config4-samples M]]
 """
 from __future__ import annotations
 
@@ -620,6 +630,36 @@ def config5_leg(P, pk, sk, coder, dev, stream, meter, per_rank: int, rank: int, 
     return out
 
 
+DUMP_SAMPLE = 1 << 14  # ciphertexts --dump-outputs writes: 16 MiB of float64 words at 2048 bits
+
+
+def pin_obfuscation(pk, rank: int) -> None:
+    """--dump-outputs: draw this key's obfuscation from a fixed ChaCha20 key and the nonces 1, 2,
+    ... (the library seeds the key from the OS and mixes the process id into the nonce), so the
+    same arguments give the same ciphertexts in every run.  Same kernels, same work."""
+    import ctypes
+    import itertools
+    words = np.random.default_rng(20241218 + rank).integers(0, 1 << 32, 8, dtype=np.uint64)
+    pk._key.rng_key = (ctypes.c_uint32 * 8)(*[int(w) for w in words])
+    nonces = itertools.count(1)
+    pk._key.next_nonce = lambda: next(nonces)
+
+
+def dump_outputs(path: str, ct, pk, rank: int) -> None:
+    """Write the ciphertext vector `ct` (what the timed step returned) under `path`: a seeded
+    sample of DUMP_SAMPLE elements in index order, exported to the reference's signed integers."""
+    n = ct.count
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20241218).choice(n, DUMP_SAMPLE, replace=False))
+        ct = ct._gather(torch.from_numpy(idx))
+    mag, neg, exp = ct.export_signed(pk)
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}.npy" if rank else ".npy"
+    np.save(os.path.join(path, "ciphertext_magnitude" + suffix), mag.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "ciphertext_negative" + suffix), neg.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "ciphertext_exp" + suffix), exp.cpu().numpy().astype(np.float32))
+
+
 def launch_ranks(nproc: int) -> int:
     """`bench.py --gpus N` (N > 1) started without a launcher: run the same command line as N
     ranks under torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) and
@@ -652,6 +692,12 @@ def main() -> None:
     ap.add_argument("--total", type=int, default=0,
                     help="BASELINE config 5: this many elements in all, split over the ranks (strong "
                          "scaling), then the ciphertext all-gather; replaces --n")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's ciphertexts (a seeded sample) as "
+                         "DIR/<name>.npy; the obfuscation is then drawn from a fixed key")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too: the op legs, other key sizes, the "
+                         "histogram, Hetero-LR and config 4/5 legs, the N>1 gathers and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip decrypt/add/e2e legs")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the ciphertext all-gather leg")
@@ -661,6 +707,8 @@ def main() -> None:
                     help="BASELINE config 5 leg (config5): elements per rank (weak: 100M at 8 GPUs), "
                          "then gather to rank 0 and all-gather; 0 skips it")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -694,6 +742,8 @@ def main() -> None:
     sk, pk, coder = P.keypair_from_primes(p, q, keyholder=False)
     pk_kh = P.keypair_from_primes(p, q, keyholder=True)[1]
     key_bits = pk.n.bit_length()
+    if args.dump_outputs:
+        pin_obfuscation(pk, rank)
 
     strong = args.total > 0
     if strong:
@@ -765,12 +815,15 @@ def main() -> None:
                     "clock_GHz_min": round(min(cs), 4), "clock_GHz_max": round(max(cs), 4)}
     progress(f"timed encrypt: {args.steps} steps in {elapsed:.1f} s")
     value = (args.total if strong else world * N) * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ct, pk, rank)
+        progress(f"outputs written to {args.dump_outputs}")
 
     # BASELINE config 5's exchange step, outside the timed region: every rank's ciphertext
     # shard all-gathered over RCCL/xGMI (fate_amd.dist.gather_tiles), so the whole vector
     # sits on each rank as the federation sender needs it.  Reported beside `value`.
     gather_info = {}
-    if dist and not args.no_gather:
+    if args.full and dist and not args.no_gather:
         from fate_amd.dist import gather_tiles, gather_tiles_to
         # onto rank 0 only (the federation sender: fate_amd.dist.gather_tiles_to, point to
         # point), then onto every rank (the all-gather)
@@ -810,7 +863,7 @@ def main() -> None:
         del Cg, sg, eg
 
     extras = {}
-    if not args.no_extras and not strong:
+    if args.full and not args.no_extras and not strong:
         # decrypt (device-resident), with the bit-exact round trip check; one untimed pass
         # first, so the timed one does not include growing the context's scratch buffer
         # (the timed pass is queued right behind it, no host sync between: the shader clock
@@ -1165,9 +1218,10 @@ def main() -> None:
                                                       world=world, iupdate_roofline=iupdate_roofline)
             torch.cuda.empty_cache()
 
-    progress("extras done")
-    # BASELINE config 5 (every line, so the driver's scaling run measures it): 12.5M per rank
-    if args.config5_per_rank > 0 and not strong:
+    if args.full:
+        progress("extras done")
+    # BASELINE config 5 (every --full line, so a scaling run measures it): 12.5M per rank
+    if args.full and args.config5_per_rank > 0 and not strong:
         del ct
         torch.cuda.empty_cache()
         extras["config5"] = config5_leg(P, pk, sk, coder, dev, stream, meter, args.config5_per_rank, rank, world,
@@ -1231,8 +1285,9 @@ def main() -> None:
         out["per_rank"] = per_rank
     out.update(gather_info)
     out.update(extras)
-    progress("config 5 leg done; CPU baseline next" if world == 1 else "config 5 leg done")
-    if world == 1 and not args.no_cpu_baseline and not strong:
+    if args.full:
+        progress("config 5 leg done; CPU baseline next" if world == 1 else "config 5 leg done")
+    if args.full and world == 1 and not args.no_cpu_baseline and not strong:
         try:
             cb = cpu_baseline(p, q)
             # GPU / CPU ratios: against the measured worker pool, one process, and the

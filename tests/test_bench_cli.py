@@ -28,6 +28,18 @@ def test_rank_command_line():
     assert tail == ["--gpus", "4", "--elements", "4096", "--steps=3", "--elements=64", "--total", "100"]
 
 
+def test_steps_must_be_positive(monkeypatch, capsys):
+    """--steps sets the number of timed steps; ms_per_step divides by it, so 0 is refused at
+    the command line, before any device call."""
+    import pytest
+
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0", "--warmup", "1"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2 and "--steps" in capsys.readouterr().err
+
+
 def test_keyholder_credit_follows_the_draw(monkeypatch):
     """rooflines' key-holder credit (bench.enc_crt_mac32_per_elem) counts the modexps that run:
     with the (z_p, z_q) draw one |p|-bit exponent mod s^2 per half, else the split (keys above
