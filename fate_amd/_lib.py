@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "fphe_fold", "fphe_fold_segments", "fphe_permute", "fphe_export_signed", "fphe_import_signed",
     "fphe_wire_lengths", "fphe_wire_encode", "fphe_wire_scan", "fphe_wire_decode", "fphe_chacha20_blocks",
     "fphe_clock_stamp", "fphe_pack_squeeze", "fphe_positions_terms",
+    "fphe_ou_ctx_create", "fphe_ou_encrypt", "fphe_ou_decrypt",
 )
 
 _lock = threading.Lock()
@@ -157,6 +158,14 @@ def load() -> ctypes.CDLL:
         lib.fphe_wire_decode.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp, vp]
         for name in ("fphe_wire_lengths", "fphe_wire_encode", "fphe_wire_scan", "fphe_wire_decode"):
             getattr(lib, name).restype = st
+        if hasattr(lib, "fphe_ou_ctx_create"):  # an A/B build from before it (FPHE_LIB_PATH) lacks it
+            lib.fphe_ou_ctx_create.argtypes = [ctypes.c_int, ctypes.c_uint32, c_u32p, c_u32p, c_u32p, c_u32p, c_u32p,
+                                               ctypes.POINTER(vp)]
+            lib.fphe_ou_ctx_create.restype = st
+            lib.fphe_ou_encrypt.argtypes = [vp, vp, ctypes.c_uint32, sz, vp, c_u32p, ctypes.c_uint64, vp, vp]
+            lib.fphe_ou_encrypt.restype = st
+            lib.fphe_ou_decrypt.argtypes = [vp, vp, sz, vp, vp]
+            lib.fphe_ou_decrypt.restype = st
         _lib = lib
         return lib
 

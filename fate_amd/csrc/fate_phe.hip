@@ -607,6 +607,62 @@ __global__ __launch_bounds__(256) void k_decode_f64(KeyArgs K, const u32* __rest
 namespace {
 #include "group_dev.h"
 #include "wide_dev.h"
+
+// ---- Okamoto-Uchiyama (ou_dev.h): the engine kernels once per radix, as kernels27.h ----------
+namespace ou27 {
+using namespace fphe::r27;
+using k27::powm27;
+#include "ou_dev.h"
+}  // namespace ou27
+namespace ou28 {
+using namespace fphe::r28;
+using k28::powm27;
+#include "ou_dev.h"
+}  // namespace ou28
+template <int TPI>
+using OU = std::conditional_t<fphe::rad_lb(TPI) == 27, ou27::Kern, ou28::Kern>;
+constexpr int kOuWin = 4;  // fixed-base window of k_ou_encrypt27 (table size against L2)
+
+// OU decrypt, second phase: m = L(y) h_p mod p from y = c^(p-1) mod p^2 (k_ou_decrypt27), with
+// the L-function and h_p product of Paillier's p half (crt_tail).  L = the context's ciphertext
+// words: y (< p^2 < n) takes L words and p fits L/2, the shapes crt_tail<2 L> works on.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_ou_decrypt_tail(KeyArgs K, const u32* __restrict__ Y, u32 ntiles,
+                                                            u32* __restrict__ Pout) {
+  constexpr int LH = L, LQ = L / 2;
+  extern __shared__ __attribute__((aligned(16))) u32 lds[];
+  const WaveCtx w = wave_ctx();
+  u32* slot = lds_slot<LQ>(lds, w.lane);
+  for (u32 tile = w.gw; tile < ntiles; tile += w.nw) {
+    const Tile Yt = make_tile(Y + (size_t)tile * LH * FPHE_WAVE, LH * 256u, w.lane);
+    const Tile Pt = make_tile(Pout + (size_t)tile * LQ * FPHE_WAVE, LQ * 256u, w.lane);
+    u32 A[LH], d[LQ];
+    tile_load<LH>(A, Yt, 0u);
+    crt_tail<2 * L>(d, A, slot, K.p, K.p_n0inv, K.pinv2, K.hpR);
+#pragma unroll
+    for (int j = 0; j < LQ; ++j) Pt.st(d[j], (u32)j * 256u);
+  }
+}
+
+// ct x pt on an OU context (fixedpoint_ou mul: plain c^pt mod n): the exponent is the plaintext
+// magnitude as it is -- no inverse, no "invalid plaintext" -- in k_mul_prep's output layout.
+template <int L>
+__global__ __launch_bounds__(256) void k_ou_mul_prep(const u32* __restrict__ P, u32 lp, int pstride, size_t count,
+                                                     u8* __restrict__ need, u32* __restrict__ Eout,
+                                                     int32_t* __restrict__ ebits_out) {
+  constexpr u32 L1 = L / 2;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t pe = pstride ? e : 0;
+    int eb = 0;
+    for (u32 j = 0; j < L1; ++j) {
+      const u32 w = j < lp ? P[tiled(pe, lp, j)] : 0u;
+      if (w) eb = 32 * (int)j + 32 - __clz(w);
+      Eout[tiled(e, L1, j)] = w;
+    }
+    need[e] = 0;
+    ebits_out[e] = eb;
+  }
+}
 }  // namespace
 
 // ======================================================================================
@@ -638,6 +694,11 @@ struct fphe_ctx {
   // draws (z_p, z_q) (effective only when kh_direct)
   int64_t wide_decrypt_max = 4096, wide_encrypt_max = 2048, wide_kh_encrypt_max = 4096;
   bool kh_direct_z = true;
+  // Okamoto-Uchiyama context (fphe_ou_ctx_create): the N2* slots of K hold n = p^2 q; ou_tab is
+  // the fixed-base table of k_ou_encrypt27 (inside blob), ou_hwin the windows of h's part
+  bool ou = false;
+  const u32* ou_tab = nullptr;
+  u32 ou_hwin = 0;
   std::mutex mu;
 };
 
@@ -1522,6 +1583,16 @@ void launch_inv27(fphe_ctx* c, const uint32_t* Ca, size_t count, const uint8_t* 
                   int32_t* err, u32* X0, hipStream_t s) {
   constexpr int TPIh = L / 64, Eh = FPHE_WAVE / TPIh, NLh = rad_ll(TPIh) * TPIh, L1 = L / 2;
   constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  if constexpr (L <= 128) {
+    if (c->ou) {  // n = p^2 q: one full-width safegcd (ou_dev.h), no lift
+      auto ko = OU<TPI>::template inv<L>();
+      const size_t ldso = (size_t)kWavesPerBlock * NL * E * 4;
+      set_lds(ko, ldso);
+      const unsigned go = occ_grid(c, ko, ldso, (count + E - 1) / E, "ou_inv27");
+      hipLaunchKernelGGL(ko, dim3(go), dim3(kBlock), ldso, s, c->K, Ca, count, need, Co, err, (u32)NL);
+      return;
+    }
+  }
   auto k1 = KS<TPIh>::template inv_n<L>();
   const size_t lds1 = (size_t)kWavesPerBlock * NLh * Eh * 4;
   set_lds(k1, lds1);
@@ -1609,11 +1680,15 @@ fphe_status launch_mul27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, con
     const uint8_t* ns = pstride ? pneg + e0 : pneg;
     const int32_t* xs = pstride ? pexp + e0 : pexp;
     const unsigned pgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 8);
-    hipLaunchKernelGGL(k_mul_prep<L>, dim3(pgrid), dim3(256), 0, s, c->K, Ps, lp, ns, pstride, m, need, Ex, eb, err);
-    if (m >= binv_min())
-      launch_binv27<L>(c, Cs, m, need, Cinv, err, X0, s);
-    else
-      launch_inv27<L>(c, Cs, m, need, Cinv, err, X0, s);
+    if (c->ou) {  // plain c^pt mod n: no sign branches, nothing to invert
+      hipLaunchKernelGGL(k_ou_mul_prep<L>, dim3(pgrid), dim3(256), 0, s, Ps, lp, pstride, m, need, Ex, eb);
+    } else {
+      hipLaunchKernelGGL(k_mul_prep<L>, dim3(pgrid), dim3(256), 0, s, c->K, Ps, lp, ns, pstride, m, need, Ex, eb, err);
+      if (m >= binv_min())
+        launch_binv27<L>(c, Cs, m, need, Cinv, err, X0, s);
+      else
+        launch_inv27<L>(c, Cs, m, need, Cinv, err, X0, s);
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Cs, Cinv, need, ea + e0, Ex, eb, xs, pstride, m,
                        Co + t0 * L * FPHE_WAVE, so + e0, eo + e0, c->scratch, (u32)NL);
     if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
@@ -1850,6 +1925,39 @@ __global__ __launch_bounds__(256) void k_import_signed(const u32* __restrict__ N
 }
 }  // namespace
 
+namespace {
+// The device half of context creation, shared by fphe_ctx_create and fphe_ou_ctx_create: the
+// path-option defaults, the CU count, the pool threshold and the key blob's upload.  Call with
+// the device current; on failure nothing is left allocated (the caller deletes c).
+fphe_status ctx_device_init(fphe_ctx* c, int device, const std::vector<u32>& blob) {
+  c->wide_decrypt_max = env_i64("FPHE_WIDE_DECRYPT_MAX", 4096);
+  c->wide_encrypt_max = env_i64("FPHE_WIDE_ENCRYPT_MAX", 2048);
+  c->wide_kh_encrypt_max = env_i64("FPHE_WIDE_KH_ENCRYPT_MAX", 4096);
+  c->kh_direct_z = env_i64("FPHE_KH_DIRECT_Z", 1) != 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FPHE_ERR_HIP;
+  c->cus = prop.multiProcessorCount;
+  {
+    // fphe_fold_segments takes its scratch from the device's default stream-ordered pool:
+    // keep up to 24 GiB of it cached across calls (the default threshold of 0 hands every
+    // block back to the driver at each synchronisation, and a 1-GiB re-map costs ms; a
+    // 200M-term histogram over 20M source ciphertexts uses ~12 GiB, of 288 GiB of HBM)
+    hipMemPool_t pool;
+    if (hipDeviceGetDefaultMemPool(&pool, device) == hipSuccess) {
+      uint64_t keep = (uint64_t)24 << 30;
+      (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+    }
+  }
+  if (hipMalloc(&c->blob, blob.size() * 4) != hipSuccess) { c->blob = nullptr; return FPHE_ERR_HIP; }
+  if (hipMemcpy(c->blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(c->blob);
+    c->blob = nullptr;
+    return FPHE_ERR_HIP;
+  }
+  return FPHE_OK;
+}
+}  // namespace
+
 extern "C" {
 
 fphe_status fphe_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, const uint32_t* p_w,
@@ -1989,29 +2097,8 @@ fphe_status fphe_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, 
     auto* c = new fphe_ctx();
     c->device = device; c->key_bits = key_bits; c->L1 = L1; c->L2 = L2; c->LQ = LQ; c->has_sk = has_sk;
     c->kh_direct = has_sk && kh_direct;
-    c->wide_decrypt_max = env_i64("FPHE_WIDE_DECRYPT_MAX", 4096);
-    c->wide_encrypt_max = env_i64("FPHE_WIDE_ENCRYPT_MAX", 2048);
-    c->wide_kh_encrypt_max = env_i64("FPHE_WIDE_KH_ENCRYPT_MAX", 4096);
-    c->kh_direct_z = env_i64("FPHE_KH_DIRECT_Z", 1) != 0;
     DevGuard g(device);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete c; return FPHE_ERR_HIP; }
-    c->cus = prop.multiProcessorCount;
-    {
-      // fphe_fold_segments takes its scratch from the device's default stream-ordered pool:
-      // keep up to 24 GiB of it cached across calls (the default threshold of 0 hands every
-      // block back to the driver at each synchronisation, and a 1-GiB re-map costs ms; a
-      // 200M-term histogram over 20M source ciphertexts uses ~12 GiB, of 288 GiB of HBM)
-      hipMemPool_t pool;
-      if (hipDeviceGetDefaultMemPool(&pool, device) == hipSuccess) {
-        uint64_t keep = (uint64_t)24 << 30;
-        (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-      }
-    }
-    if (hipMalloc(&c->blob, blob.size() * 4) != hipSuccess) { delete c; return FPHE_ERR_HIP; }
-    if (hipMemcpy(c->blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(c->blob); delete c; return FPHE_ERR_HIP;
-    }
+    if (ctx_device_init(c, device, blob) != FPHE_OK) { delete c; return FPHE_ERR_HIP; }
     u32* b = c->blob;
     KeyArgs& K = c->K;
     K.N2 = b + o_N2; K.N2_R2 = b + o_N2R2; K.N2_R1 = b + o_N2R1; K.n = b + o_n; K.nm1 = b + o_nm1;
@@ -2120,6 +2207,7 @@ fphe_status fphe_encode_f64(const fphe_ctx* c, const double* x, size_t count, ui
 fphe_status fphe_decode_f32(const fphe_ctx* c, const uint32_t* P, uint32_t lp, const int32_t* exp, size_t count,
                             float* out, int32_t* err, void* stream) {
   if (!c || !err) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
@@ -2136,6 +2224,7 @@ fphe_status fphe_decode_f32(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
 fphe_status fphe_decode_f64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, const int32_t* exp, size_t count,
                             double* out, int32_t* err, void* stream) {
   if (!c || !err) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
@@ -2153,6 +2242,7 @@ fphe_status fphe_decode_f64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
 fphe_status fphe_encode_i64(const fphe_ctx* c, const int64_t* x, size_t count, uint32_t* P, uint8_t* neg,
                             int32_t* exp, void* stream) {
   if (!c) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!x || !P || !neg || !exp) return FPHE_ERR_ARG;
   DevGuard g(c->device);
@@ -2169,6 +2259,7 @@ fphe_status fphe_encode_i64(const fphe_ctx* c, const int64_t* x, size_t count, u
 fphe_status fphe_decode_i64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, const int32_t* exp, size_t count,
                             int64_t* out, int32_t* err, void* stream) {
   if (!c || !err) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
@@ -2185,6 +2276,7 @@ fphe_status fphe_decode_i64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
 fphe_status fphe_decode_i32(const fphe_ctx* c, const uint32_t* P, uint32_t lp, const int32_t* exp, size_t count,
                             int32_t* out, int32_t* err, void* stream) {
   if (!c || !err) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
@@ -2242,6 +2334,7 @@ fphe_status fphe_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, const uint
                          const uint32_t* r, const uint32_t rng_key[8], uint64_t nonce, uint32_t* C, uint8_t* sign,
                          void* stream) {
   if (!c) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (count == 0) return FPHE_OK;
   if (!P || !neg || !C || !sign || lp == 0 || lp > (uint32_t)c->L1) return FPHE_ERR_ARG;
   if (count >= (1ull << 32)) return FPHE_ERR_ARG;
@@ -2260,6 +2353,7 @@ fphe_status fphe_encrypt_crt(fphe_ctx* c, const uint32_t* P, uint32_t lp, const 
                              const uint32_t* r, const uint32_t rng_key[8], uint64_t nonce, uint32_t* C,
                              uint8_t* sign, void* stream) {
   if (!c) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (!c->has_sk) return FPHE_ERR_NO_SK;
   if (count == 0) return FPHE_OK;
   if (!P || !neg || !C || !sign || lp == 0 || lp > (uint32_t)c->L1) return FPHE_ERR_ARG;
@@ -2338,6 +2432,7 @@ fphe_status fphe_positions_terms(const void* positions, int pos_i64, size_t ns, 
 
 fphe_status fphe_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, void* stream) {
   if (!c) return FPHE_ERR_ARG;
+  if (c->ou) return FPHE_ERR_ARG;  // reads the Paillier key material (include/fate_phe.h)
   if (!c->has_sk) return FPHE_ERR_NO_SK;
   if (count == 0) return FPHE_OK;
   if (!C || !P) return FPHE_ERR_ARG;
@@ -2478,6 +2573,7 @@ fphe_status fphe_mul(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, const i
   if (!c || !err) return FPHE_ERR_ARG;
   if (count == 0) return FPHE_OK;
   if (!Ca || !sa || !ea || !P || !pneg || !pexp || !Co || !so || !eo || lp == 0) return FPHE_ERR_ARG;
+  if (c->ou && lp > (uint32_t)c->L1) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
   if (c->L2 == 256)
@@ -2671,6 +2767,289 @@ fphe_status fphe_clock_stamp(uint64_t* out, uint32_t blocks, uint32_t* wall_khz,
   }
   hipLaunchKernelGGL(k_clock_stamp, dim3(blocks), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)out);
   return hip_ok(hipGetLastError());
+}
+
+}  // extern "C"
+
+// ======================================================================================
+// Okamoto-Uchiyama (rust/fate_utils/crates/ou/src/lib.rs:69-138): context, encrypt, decrypt.
+// Every other entry point reaches an OU context through the N2* slots of KeyArgs, which hold
+// n = p^2 q.
+// ======================================================================================
+namespace {
+
+// Host Montgomery products (32-bit CIOS, R = 2^(32 L)) for the setup work hbn::mod is too slow
+// for: g^(p-1) mod p^2 and the ~10^4 products of the fixed-base tables.
+struct HostMont {
+  Limbs N, R2;
+  size_t L;
+  u32 n0;
+  HostMont(const Limbs& n, size_t l) : N(hbn::padded(n, l)), R2(hbn::padded(hbn::pow2_mod(64 * l, n), l)), L(l),
+                                       n0(hbn::neg_inv32(n[0])) {}
+  // a b R^-1 mod N for a, b < N (L words each)
+  Limbs mul(const Limbs& a, const Limbs& b) const {
+    std::vector<u32> t(L + 2, 0u);
+    for (size_t i = 0; i < L; ++i) {
+      u64 c = 0;
+      for (size_t j = 0; j < L; ++j) {
+        const u64 s = (u64)a[j] * b[i] + t[j] + c;
+        t[j] = (u32)s;
+        c = s >> 32;
+      }
+      u64 s = (u64)t[L] + c;
+      t[L] = (u32)s;
+      t[L + 1] = (u32)(s >> 32);
+      const u32 m = t[0] * n0;
+      c = ((u64)m * N[0] + t[0]) >> 32;
+      for (size_t j = 1; j < L; ++j) {
+        s = (u64)m * N[j] + t[j] + c;
+        t[j - 1] = (u32)s;
+        c = s >> 32;
+      }
+      s = (u64)t[L] + c;
+      t[L - 1] = (u32)s;
+      t[L] = t[L + 1] + (u32)(s >> 32);
+    }
+    // t < 2N: one conditional subtraction, in place
+    bool ge = t[L] != 0;
+    if (!ge) {
+      ge = true;  // t == N counts
+      for (size_t j = L; j-- > 0;)
+        if (t[j] != N[j]) { ge = t[j] > N[j]; break; }
+    }
+    if (ge) {
+      u64 br = 0;
+      for (size_t j = 0; j < L; ++j) {
+        const u64 d = (u64)t[j] - N[j] - br;
+        t[j] = (u32)d;
+        br = d >> 63;
+      }
+    }
+    t.resize(L);
+    return t;
+  }
+  Limbs to(const Limbs& x) const { return mul(hbn::padded(x, L), R2); }  // x R
+  Limbs from(const Limbs& X) const {                                       // X R^-1
+    Limbs one(L, 0u);
+    one[0] = 1;
+    return mul(X, one);
+  }
+  // x^e mod N (plain in, plain out), x < N
+  Limbs pow(const Limbs& x, const Limbs& e) const {
+    const Limbs X = to(x);
+    Limbs A = to(Limbs{1});
+    for (size_t i = hbn::bitlen(e); i-- > 0;) {
+      A = mul(A, A);
+      if (hbn::bit(e, i)) A = mul(A, X);
+    }
+    return hbn::norm(from(A));
+  }
+};
+
+// rows of the fixed-base table (ou_dev.h) for one base: M(base^(d 2^(W i))) for i < nwin,
+// d = 1 .. 2^W - 1, as NL limbs of LB bits, appended to `out`.  Reng = 2^(LB NL) mod n.
+void ou_table_rows(const HostMont& M, const Limbs& base, u32 nwin, const Limbs& Reng, int NL, int LB,
+                   std::vector<u32>& out) {
+  constexpr u32 D = (1u << kOuWin) - 1u;
+  Limbs b = M.to(base);  // base^(2^(W i)) in the host's Montgomery form
+  for (u32 i = 0; i < nwin; ++i) {
+    Limbs e = b;
+    for (u32 d = 1; d <= D; ++d) {
+      const Limbs row = to_radix(hbn::norm(M.mul(e, Reng)), NL, LB);  // (x R32)(R_eng) / R32 = x R_eng
+      out.insert(out.end(), row.begin(), row.end());
+      e = M.mul(e, b);
+    }
+    b = e;  // base^(2^W 2^(W i))
+  }
+}
+
+template <int L>
+fphe_status launch_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
+                              const uint32_t key[8], uint64_t nonce, uint32_t* C, hipStream_t s) {
+  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  auto kern = OU<TPI>::template encrypt<L, kOuWin>();
+  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
+  set_lds(kern, lds);
+  const size_t span = span_elems(c, kern, lds, E);
+  const size_t m0 = count < span ? count : span;
+  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "ou_encrypt27");
+  const size_t rbytes = (size_t)ntiles_of(m0) * L * FPHE_WAVE * 4;
+  ChaChaKey ck;
+  if (!r) {
+    for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
+    if (ensure_scratch(c, rbytes, s) != FPHE_OK) return FPHE_ERR_HIP;
+  }
+  for (size_t e0 = 0; e0 < count; e0 += span) {  // spans run in stream order over one scratch
+    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
+    const u32* rbuf = r ? r + t0 * L * FPHE_WAVE : nullptr;
+    if (!r) {  // draw_r over the L words of n (K.nm1, K.nbits of an OU context)
+      const unsigned rgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 4);
+      hipLaunchKernelGGL(k_draw_r<L>, dim3(rgrid), dim3(256), 0, s, c->K, m, ck, nonce, e0, c->scratch);
+      rbuf = c->scratch;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, c->ou_tab, c->ou_hwin, P + t0 * lp * FPHE_WAVE, lp,
+                       rbuf, m, C + t0 * L * FPHE_WAVE, (u32)NL);
+    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
+  }
+  return FPHE_OK;
+}
+
+template <int L>
+fphe_status launch_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, hipStream_t s) {
+  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, LQ = L / 2;
+  auto kern = OU<TPI>::template decrypt<L, kWinSlide>();
+  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
+  set_lds(kern, lds);
+  const size_t span = span_elems(c, kern, lds, E);
+  const size_t m0 = count < span ? count : span;
+  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "ou_decrypt27");
+  const size_t tbytes = (size_t)grid * kWavesPerBlock * kTabEntries<kWinSlide> * rad_ll(TPI) * FPHE_WAVE * 4;
+  const size_t ybytes = (size_t)ntiles_of(m0) * L * FPHE_WAVE * 4;
+  if (ensure_scratch(c, tbytes + ybytes, s) != FPHE_OK) return FPHE_ERR_HIP;
+  u32* Y = c->scratch + tbytes / 4;
+  auto ktail = k_ou_decrypt_tail<L>;
+  const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;
+  set_lds(ktail, lds2);
+  for (size_t e0 = 0; e0 < count; e0 += span) {
+    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, C + t0 * L * FPHE_WAVE, m, Y, c->scratch, (u32)NL);
+    hipLaunchKernelGGL(ktail, dim3(grid_for(c, m, bpc_for_slot(LQ))), dim3(kBlock), lds2, s, c->K, (const u32*)Y,
+                       ntiles_of(m), P + t0 * LQ * FPHE_WAVE);
+    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
+  }
+  return FPHE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fphe_status fphe_ou_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, const uint32_t* g_w,
+                               const uint32_t* h_w, const uint32_t* p_w, const uint32_t* q_w, fphe_ctx** out) {
+  if (!out || !n_w || !g_w || !h_w) return FPHE_ERR_ARG;
+  if (key_bits < 1024 || key_bits > 4096 || key_bits % 2) return FPHE_ERR_ARG;
+  if ((p_w == nullptr) != (q_w == nullptr)) return FPHE_ERR_ARG;
+  const int L2 = key_bits <= 2048 ? 64 : 128, L1 = L2 / 2;
+  try {
+    const Limbs n = from_words(n_w, L2), g = from_words(g_w, L2), h = from_words(h_w, L2);
+    if (n.empty() || !(n[0] & 1)) return FPHE_ERR_KEY;
+    if (hbn::bitlen(n) != key_bits) return FPHE_ERR_KEY;  // ou/src/lib.rs:80 keeps bits(n) == bit_length
+    if (g.empty() || h.empty() || hbn::cmp(g, n) >= 0 || hbn::cmp(h, n) >= 0) return FPHE_ERR_KEY;
+    std::vector<u32> blob;
+    auto put = [&](const Limbs& v, size_t len) -> size_t {
+      const size_t off = blob.size();
+      Limbs p = hbn::padded(v, len);
+      blob.insert(blob.end(), p.begin(), p.end());
+      while (blob.size() % 4) blob.push_back(0);  // 16-byte aligned sections
+      return off;
+    };
+    const int TPI2 = L2 / 32, LB2 = rad_lb(TPI2), NL2 = rad_ll(TPI2) * TPI2;
+    const Limbs Reng = hbn::pow2_mod((size_t)LB2 * NL2, n);
+    const size_t o_N2 = put(n, L2);
+    const size_t o_n = put(n, L2 + 1);
+    const size_t o_nm1 = put(hbn::sub(n, Limbs{1}), L2);
+    const size_t o_N2_27 = put(to_radix(n, NL2, LB2), NL2);
+    const size_t o_N2R1_27 = put(to_radix(Reng, NL2, LB2), NL2);
+    const size_t o_N2R2_27 = put(to_radix(hbn::pow2_mod((size_t)2 * LB2 * NL2, n), NL2, LB2), NL2);
+    const size_t o_N2R3_27 = put(to_radix(hbn::pow2_mod((size_t)3 * LB2 * NL2, n), NL2, LB2), NL2);
+    const size_t o_N2M1 = put(Reng, L2);
+    size_t o_P2_27 = 0, o_P2R1_27 = 0, o_pm1 = 0, o_p = 0, o_pinv2 = 0, o_hpR = 0;
+    u32 p2n0 = 0, pn0 = 0;
+    int pm1b = 0, pb = 0;
+    const bool has_sk = p_w != nullptr;
+    if (has_sk) {
+      const Limbs p = from_words(p_w, L1), q = from_words(q_w, L1);
+      if (p.empty() || q.empty() || !(p[0] & 1) || !(q[0] & 1)) return FPHE_ERR_KEY;
+      if (hbn::cmp(p, q) == 0) return FPHE_ERR_KEY;
+      const Limbs P2 = hbn::mul(p, p);
+      if (hbn::cmp(hbn::mul(P2, q), n) != 0) return FPHE_ERR_KEY;
+      const Limbs pm1 = hbn::sub(p, Limbs{1});
+      // h_p = L(g^(p-1) mod p^2)^-1 mod p, L(x) = (x - 1) / p (ou/src/lib.rs:120-131); a g whose
+      // power is 1 has no inverse: inv_mod throws, FPHE_ERR_KEY
+      const HostMont MP(P2, (size_t)L2);
+      const Limbs y = MP.pow(hbn::mod(g, P2), pm1);
+      if (y.empty()) return FPHE_ERR_KEY;
+      const Limbs ym1 = hbn::sub(y, Limbs{1});
+      // exact quotient (y - 1) / p by the inverse of p mod 2^(32 L1), as crt_tail does
+      Limbs Lg = hbn::mul(hbn::padded(ym1, (size_t)L2), hbn::inv_pow2(p, (size_t)L1));
+      Lg.resize((size_t)L1, 0u);
+      const Limbs hp = hbn::inv_mod(hbn::norm(Lg), p);
+      o_P2_27 = put(to_radix(P2, NL2, LB2), NL2);
+      o_P2R1_27 = put(to_radix(hbn::pow2_mod((size_t)LB2 * NL2, P2), NL2, LB2), NL2);
+      o_pm1 = put(pm1, L1 + 1);
+      o_p = put(p, L1);
+      o_pinv2 = put(hbn::inv_pow2(p, (size_t)L1), L1);
+      o_hpR = put(hbn::mod(hbn::mul(hp, hbn::pow2_mod((size_t)32 * L1, p)), p), L1);
+      p2n0 = hbn::neg_inv32(P2[0]);
+      pn0 = hbn::neg_inv32(p[0]);
+      pm1b = (int)hbn::bitlen(pm1);
+      pb = (int)hbn::bitlen(p);
+    }
+    // fixed-base tables (ou_dev.h): row 0 = M(1), then h's windows over bits(n), then g's over
+    // the L1 plaintext words a call may pass
+    const u32 hwin = (key_bits + kOuWin - 1) / kOuWin, gwin = (u32)L1 * 32u / kOuWin;
+    while (blob.size() % 64) blob.push_back(0);
+    const size_t o_tab = blob.size();
+    {
+      const HostMont MN(n, (size_t)L2);
+      const Limbs RengP = hbn::padded(Reng, (size_t)L2);
+      const Limbs one = to_radix(Reng, NL2, LB2);
+      blob.reserve(blob.size() + (size_t)(1 + ((1u << kOuWin) - 1u) * (hwin + gwin)) * NL2);
+      blob.insert(blob.end(), one.begin(), one.end());
+      ou_table_rows(MN, h, hwin, RengP, NL2, LB2, blob);
+      ou_table_rows(MN, g, gwin, RengP, NL2, LB2, blob);
+    }
+    auto* c = new fphe_ctx();
+    c->device = device; c->key_bits = key_bits; c->L1 = L1; c->L2 = L2; c->LQ = L1 / 2; c->has_sk = has_sk;
+    c->ou = true;
+    c->ou_hwin = hwin;
+    // (the wide_* path options are stored and read back but select nothing on an OU context)
+    DevGuard dg(device);
+    if (ctx_device_init(c, device, blob) != FPHE_OK) { delete c; return FPHE_ERR_HIP; }
+    u32* b = c->blob;
+    KeyArgs& K = c->K;
+    K.N2 = b + o_N2; K.n = b + o_n; K.nm1 = b + o_nm1;
+    K.n2_n0inv = hbn::neg_inv32(n[0]);
+    K.nbits = (int)key_bits;
+    K.N2_27 = b + o_N2_27; K.N2R1_27 = b + o_N2R1_27; K.N2R2_27 = b + o_N2R2_27; K.N2R3_27 = b + o_N2R3_27;
+    K.n2_np27 = K.n2_n0inv & ((1u << LB2) - 1u);
+    K.N2M1 = b + o_N2M1;
+    K.nn_inv27 = (0u - K.n2_n0inv) & ((1u << LB2) - 1u);  // n^-1 mod 2^LB, k_ou_inv27's safegcd
+    if (has_sk) {
+      K.P2_27 = b + o_P2_27; K.P2R1_27 = b + o_P2R1_27; K.p2_np27 = p2n0 & ((1u << LB2) - 1u);
+      K.pm1 = b + o_pm1; K.pm1_bits = pm1b; K.p = b + o_p; K.p_bits = pb; K.p_n0inv = pn0;
+      K.pinv2 = b + o_pinv2; K.hpR = b + o_hpR;
+    }
+    c->ou_tab = b + o_tab;
+    *out = c;
+    return FPHE_OK;
+  } catch (...) {
+    return FPHE_ERR_KEY;
+  }
+}
+
+fphe_status fphe_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
+                            const uint32_t rng_key[8], uint64_t nonce, uint32_t* C, void* stream) {
+  if (!c || !c->ou) return FPHE_ERR_ARG;
+  if (count == 0) return FPHE_OK;
+  if (!P || !C || lp == 0 || lp > (uint32_t)c->L1) return FPHE_ERR_ARG;
+  if (count >= (1ull << 32)) return FPHE_ERR_ARG;
+  if (!r && !rng_key) return FPHE_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard g(c->device);
+  if (c->L2 == 128) return launch_ou_encrypt<128>(c, P, lp, count, r, rng_key, nonce, C, (hipStream_t)stream);
+  return launch_ou_encrypt<64>(c, P, lp, count, r, rng_key, nonce, C, (hipStream_t)stream);
+}
+
+fphe_status fphe_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, void* stream) {
+  if (!c || !c->ou) return FPHE_ERR_ARG;
+  if (!c->has_sk) return FPHE_ERR_NO_SK;
+  if (count == 0) return FPHE_OK;
+  if (!C || !P) return FPHE_ERR_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DevGuard g(c->device);
+  if (c->L2 == 128) return launch_ou_decrypt<128>(c, C, count, P, (hipStream_t)stream);
+  return launch_ou_decrypt<64>(c, C, count, P, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -216,6 +216,10 @@ class _KeyCtx:
         # geometry: the 1024-, 2048- or 4096-bit kernels, n zero-padded up to it
         self.L1 = 32 if self.key_bits <= 1024 else (64 if self.key_bits <= 2048 else 128)
         self.L2 = 2 * self.L1
+        self.modulus = n * n  # the ciphertext modulus (n itself for another scheme's key, fate_amd.ou)
+        self._setup()
+
+    def _setup(self) -> None:
         self._ctx: Dict[int, ctypes.c_void_p] = {}
         self._one: Dict[int, torch.Tensor] = {}
         self._lock = threading.Lock()
@@ -244,17 +248,10 @@ class _KeyCtx:
             if c is not None:
                 return c
             lib = _lib.load()
-            nw = (ctypes.c_uint32 * self.L1)(*ints_to_limbs([self.n], self.L1)[0].tolist())
-            pw = qw = None
-            if self.p is not None:
-                lq = self.L1 // 2
-                pw = (ctypes.c_uint32 * lq)(*ints_to_limbs([self.p], lq)[0].tolist())
-                qw = (ctypes.c_uint32 * lq)(*ints_to_limbs([self.q], lq)[0].tolist())
             if self._closed:
                 raise RuntimeError("key context used after its teardown (process exit): stop the threads "
                                    "that use fate_amd before the interpreter exits")
-            out = ctypes.c_void_p()
-            _lib.check(lib.fphe_ctx_create(idx, self.key_bits, nw, pw, qw, ctypes.byref(out)), "fphe_ctx_create")
+            out = self._create(lib, idx)
             with _OPTIONS_LOCK:
                 for opt, val in _PATH_OPTIONS.items():
                     _lib.check(lib.fphe_ctx_set_option(out, opt, val), "fphe_ctx_set_option")
@@ -265,6 +262,18 @@ class _KeyCtx:
                 atexit.register(_teardown_contexts)
                 _TEARDOWN_REGISTERED = True
             return out
+
+    def _create(self, lib, idx: int) -> ctypes.c_void_p:
+        """A new device context of this key on device `idx` (fphe_ctx_create)."""
+        nw = (ctypes.c_uint32 * self.L1)(*ints_to_limbs([self.n], self.L1)[0].tolist())
+        pw = qw = None
+        if self.p is not None:
+            lq = self.L1 // 2
+            pw = (ctypes.c_uint32 * lq)(*ints_to_limbs([self.p], lq)[0].tolist())
+            qw = (ctypes.c_uint32 * lq)(*ints_to_limbs([self.q], lq)[0].tolist())
+        out = ctypes.c_void_p()
+        _lib.check(lib.fphe_ctx_create(idx, self.key_bits, nw, pw, qw, ctypes.byref(out)), "fphe_ctx_create")
+        return out
 
     def close(self) -> None:
         """Destroy this key's device contexts (device memory, side stream, events) after the
@@ -290,6 +299,10 @@ class _KeyCtx:
 
 
 _KEYS: Dict[Tuple[int, Optional[int]], _KeyCtx] = {}
+# public keys of another scheme by their modulus (fate_amd.ou registers its n = p^2 q): a vector
+# carries only its modulus, and _key_for(n) must give it that scheme's context, not a Paillier
+# context of the same n
+_SCHEME_KEYS: Dict[int, _KeyCtx] = {}
 _KEYS_LOCK = threading.Lock()
 _TEARDOWN_REGISTERED = False
 
@@ -397,6 +410,8 @@ def path_option(device: torch.device, key: "_KeyCtx", name: str) -> int:
 def _key_for(n: int, p: Optional[int] = None, q: Optional[int] = None) -> _KeyCtx:
     """One device context per (key, public/private) per process, shared by PK/SK/Coder."""
     with _KEYS_LOCK:
+        if p is None and n in _SCHEME_KEYS:
+            return _SCHEME_KEYS[n]
         k = _KEYS.get((n, p))
         if k is None:
             k = _KEYS[(n, p)] = _KeyCtx(n, p, q)
@@ -468,7 +483,7 @@ def _resolve(v: "CiphertextVector", n: int) -> None:
         rows = torch.cat([rows, rows.new_zeros((rows.shape[0], L2 - rows.shape[1]))], 1)
     rows = rows.contiguous()
     if v.count:
-        _check_below(rows, n * n)
+        _check_below(rows, key.modulus)
     cv = CiphertextVector.import_signed(PK(n), rows, v.sign[: v.count].contiguous(), v.exp[: v.count])
     v.C, v.sign, v.exp, v.n, v.raw = cv.C, cv.sign, cv.exp, n, False
     del dev

@@ -388,6 +388,51 @@ fphe_status fphe_chacha20_blocks(const uint32_t key[8], uint32_t counter, const 
  * clock between them (the cycle counters of different CUs are not synchronised). */
 fphe_status fphe_clock_stamp(uint64_t* out, uint32_t blocks, uint32_t* wall_khz, void* stream);
 
+/* (9) Okamoto-Uchiyama, FATE's second PHE scheme (`kind: ou`; rust/fate_utils/crates/ou/src/lib.rs:
+ * 69-138, fixedpoint_ou/src/lib.rs, fate_utils/src/ou/ou.rs).  n = p^2 q, h = g^n mod n,
+ * encrypt(m) = g^m h^r mod n, decrypt(c) = L(c^(p-1) mod p^2) L(g^(p-1) mod p^2)^-1 mod p with
+ * L(x) = (x - 1) / p.  An OU context is an fphe_ctx whose ciphertext modulus is n:
+ *   - vectors are (C, sign, exp) with C = M(c) = c R mod n (canonical), L2 = 64 words for
+ *     key_bits <= 2048 and 128 up to 4096 (smaller moduli zero-padded); sign is always 0;
+ *     plaintexts are unsigned magnitudes of at most L1 = L2 / 2 words (neg is ignored);
+ *   - fphe_add, fphe_add_ordered, fphe_neg, fphe_fold, fphe_fold_segments, fphe_sqmul,
+ *     fphe_pack_squeeze, fphe_align, fphe_export_signed, fphe_import_signed, fphe_ctx_limbs,
+ *     fphe_ctx_mont_one, fphe_ctx_destroy and the option calls take it as they take a Paillier
+ *     context and compute mod n (fphe_neg: the inverse mod n, fixedpoint_ou neg);
+ *   - fphe_mul computes the plain c^pt mod n of fixedpoint_ou's mul: pneg is ignored, lp <= L1,
+ *     and FPHE_EF_MUL_INVALID_PT is never set;
+ *   - fphe_encrypt, fphe_encrypt_crt, fphe_decrypt and the codecs that read the Paillier key
+ *     (fphe_decode_f32/f64, fphe_encode_i64, fphe_decode_i64/i32) return FPHE_ERR_ARG;
+ *     fphe_encode_f32/f64, fphe_pack_f64 and fphe_unpack_f64 read no key and work;
+ *   - only throughput kernels exist for OU: calls of any size run them, and the
+ *     FPHE_OPT_WIDE_* / FPHE_OPT_KH_DIRECT_Z options are stored but select nothing.
+ * fphe_ou_ctx_create: n, g, h are L2 words each, p and q L1 words each (zero-padded), or both
+ * NULL for a public-only context.  key_bits = bits(n): any even size 1024..4096 (1024 is FATE's
+ * minimum_key_size for ou).  FPHE_ERR_KEY for an even n, bits(n) != key_bits, p == q,
+ * n != p^2 q, g or h outside [1, n-1], or a g with g^(p-1) mod p^2 == 1.  Creation builds the
+ * fixed-base tables of fphe_ou_encrypt on the host, for a public-only and a private context
+ * alike (either encrypts): ~11.5k 64-word products at 2048 bits, ~23k 128-word ones at 4096.
+ * Measured with the upload: ~70-90 ms per context up to 2048 bits, ~0.6 s at 3072 bits (about
+ * 1.2 s at 4096); the table takes 3.4 MB of device memory up to 2048 bits, 14.5 MB above. */
+fphe_status fphe_ou_ctx_create(int device, uint32_t key_bits, const uint32_t* n, const uint32_t* g,
+                               const uint32_t* h, const uint32_t* p, const uint32_t* q, fphe_ctx** out);
+
+/* PK.encrypt_encoded of fate_utils.ou (ou.rs; fixedpoint_ou PK::encrypt_encoded -> ou/src/lib.rs:
+ * 100-108): C = M(g^m h^r mod n), by fixed-base windowed exponentiation (no squarings).  The
+ * reference applies h^r whatever its `obfuscate` argument says (lib.rs:103), so there is no such
+ * argument here; it leaves the product of the two powers unreduced, this writes the canonical
+ * residue.  P: magnitudes [T][lp][64], lp <= L1; a plaintext >= p is not an
+ * error (it decrypts mod p, as in the reference).  r == NULL draws r uniform in [1, n-1] by
+ * rejection from element e's ChaCha20 stream (the rule of fphe_encrypt over the L2 words of n:
+ * ceil(L2 / 16) blocks per attempt); else r is injected as [T][L2][64] (parity mode).  The
+ * caller sets sign (0) and exp.  FPHE_ERR_ARG on a Paillier context. */
+fphe_status fphe_ou_encrypt(fphe_ctx* ctx, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
+                            const uint32_t rng_key[8], uint64_t rng_nonce, uint32_t* C, void* stream);
+
+/* SK.decrypt_to_encoded of fate_utils.ou (ou/src/lib.rs:120-131): P [T][L1][64] = m in [0, p).
+ * FPHE_ERR_NO_SK on a public-only context, FPHE_ERR_ARG on a Paillier context. */
+fphe_status fphe_ou_decrypt(fphe_ctx* ctx, const uint32_t* C, size_t count, uint32_t* P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
