@@ -6,6 +6,11 @@
 // TPI 4, 28-bit below: mont27_dev.h);
 // the codec, CRT-tail, permutation and wire kernels take one element per lane.  All run
 // grid-stride loops over 64-element tiles; see DESIGN.md for layouts and rooflines.
+//
+// This file: the element-per-lane Paillier kernels (draws, CRT tail, codec), the includes of the
+// other device headers (*_dev.h, kernels27.h), then the host side -- context, launch helpers
+// (size dispatch, engine geometry, spans), launchers, C ABI.  The key blob a context uploads is
+// built by plain C++ in key_blob.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,7 +22,7 @@
 #include "../../include/fate_phe.h"
 #include "mont_dev.h"
 #include "chacha_dev.h"
-#include "host_bn.h"
+#include "key_blob.h"  // host-only: KeyArgs (key_args.h), the blob builder, hbn
 
 using namespace fphe;
 
@@ -54,55 +59,9 @@ constexpr int kWinMul = 4;       // window of the per-lane-exponent modexp (ct x
 #ifndef FPHE_MUL_ADAPT
 #define FPHE_MUL_ADAPT 1  // ct x pt: 3-bit window for short exponents, all-zero windows skipped
 #endif
-constexpr int kMulShortBits = 64;
+constexpr int kMulShortBits = 64;        // waves whose longest exponent fits this take a 3-bit window
 constexpr u32 kAddRegions = 8;          // k_add27: one run of wave tiles per XCD (blocks b, b + 8, ...)
-constexpr u32 kAddCounterStride = 32;   // the runs' tile counters, 128 B apart  // waves whose longest exponent fits this take a 3-bit window
-
-// Uniform key material, passed by value (lands in the kernarg segment -> SGPRs).
-struct KeyArgs {
-  const u32* N2;       // n^2                     [L2]
-  const u32* N2_R2;    // R^2 mod n^2, R=2^(32 L2) [L2]
-  const u32* N2_R1;    // R mod n^2 (Montgomery 1) [L2]
-  const u32* n;        // n, padded               [L1+1]
-  const u32* nm1;      // n-1                     [L1]
-  const u32* max_int;  // floor(n/2)              [L1]
-  const u32* n_mm;     // n - max_int             [L1]
-  u32 n2_n0inv;
-  int nbits;
-  // private half (valid iff has_sk)
-  const u32* P2; const u32* P2_R3; const u32* pm1; const u32* p; const u32* pinv2; const u32* hpR;
-  const u32* Q2; const u32* Q2_R3; const u32* qm1; const u32* q; const u32* qinv2; const u32* hqR;
-  const u32* pinvqR;   // p^{-1} mod q, times R_q mod q
-  u32 p2_n0inv, p_n0inv, q2_n0inv, q_n0inv;
-  int pm1_bits, qm1_bits;
-  // reduced-radix engine (kernels27.h): LB-bit limbs (27 for n^2 of 2048-bit keys, 28 for
-  // every other modulus), R = 2^(LB NL); the _27 suffix names the engine, not the radix
-  const u32* N2_27; const u32* N2R1_27; const u32* N2R2_27;  // n^2, R mod n^2, R^2 mod n^2 [NL2]
-  const u32* P2_27; const u32* P2R1_27; const u32* P2R2_27;  // p^2 ...                      [NLh]
-  const u32* Q2_27; const u32* Q2R1_27; const u32* Q2R2_27;
-  u32 n2_np27, p2_np27, q2_np27;                             // -N^{-1} mod 2^LB
-  const u32* Nn_27; const u32* NnR1_27; const u32* NnR2_27;  // n, R mod n, R^2 mod n    [NLh]
-  u32 nn_np27, nn_inv27;                                     // -n^{-1}, n^{-1} mod 2^LB
-  // key-holder (CRT) encryption, valid iff has_sk: r^n mod s^2 = r^(n mod s(s-1)) mod s^2,
-  // recombined as x_p Kp + x_q Kq mod n^2 (Kp = q^2 (q^-2 mod p^2), Kq = p^2 (p^-2 mod q^2))
-  const u32* ep; const u32* eq;          // n mod p(p-1), n mod q(q-1)           [L1]
-  int ep_bits, eq_bits;
-  const u32* KpR_27; const u32* KqR_27;  // Kp R, Kq R mod n^2 (R = 2^(LB NL2))         [NL2]
-  // Montgomery-resident ciphertexts: vectors hold M(c) = c R mod n^2 with the
-  // n^2 engine's R.  R^3 mod n^2 takes a plain value x to x R^2 in one product (inverses,
-  // the key-holder nude factor); R_s^2 R^-1 mod s^2 takes M(c) mod s^2 to c R_s (decrypt).
-  const u32* N2R3_27;                    // R^3 mod n^2                                  [NL2]
-  const u32* P2RX_27; const u32* Q2RX_27;  // R_s^2 R^-1 mod s^2, s = p, q                [NLh]
-  const u32* N2M1;                       // M(1) = R mod n^2 in 32-bit words (literal 1)  [L2]
-  // key-holder encryption in two steps (FPHE_KH_SPLIT): z_s = r^(e_s)
-  // mod s with e_p = q mod (p-1), e_q = p mod (q-1), on the engine of s (TPIs = L2/128 lanes,
-  // at least 1), then x_s = z_s^s mod s^2 on the s^2 engine
-  const u32* Ps_27; const u32* PsR2_27; const u32* PsR3_27;  // p, R_s^2, R_s^3 mod p      [NLs]
-  const u32* Qs_27; const u32* QsR2_27; const u32* QsR3_27;
-  u32 ps_np27, qs_np27;
-  const u32* e1p; const u32* e1q;        // q mod (p-1), p mod (q-1)                   [LQ]
-  int e1p_bits, e1q_bits, p_bits, q_bits;
-};
+constexpr u32 kAddCounterStride = 32;   // the runs' tile counters, 128 B apart
 
 __device__ __forceinline__ void set_err(int32_t* err, u32 f) {
   if (f) atomicOr(err, (int32_t)f);
@@ -621,7 +580,6 @@ using k28::powm27;
 }  // namespace ou28
 template <int TPI>
 using OU = std::conditional_t<fphe::rad_lb(TPI) == 27, ou27::Kern, ou28::Kern>;
-constexpr int kOuWin = 4;  // fixed-base window of k_ou_encrypt27 (table size against L2)
 
 // OU decrypt, second phase: m = L(y) h_p mod p from y = c^(p-1) mod p^2 (k_ou_decrypt27), with
 // the L-function and h_p product of Paillier's p half (crt_tail).  L = the context's ciphertext
@@ -665,6 +623,10 @@ __global__ __launch_bounds__(256) void k_ou_mul_prep(const u32* __restrict__ P, 
 }
 }  // namespace
 
+#include "positions_dev.h"
+#include "wire_dev.h"
+#include "vector_dev.h"
+
 // ======================================================================================
 // host side: context + C ABI
 // ======================================================================================
@@ -704,8 +666,6 @@ struct fphe_ctx {
 
 namespace {
 
-using hbn::Limbs;
-
 fphe_status hip_ok(hipError_t e) { return e == hipSuccess ? FPHE_OK : FPHE_ERR_HIP; }
 
 struct DevGuard {
@@ -728,19 +688,41 @@ struct StreamDevGuard {
   ~StreamDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-Limbs from_words(const uint32_t* w, size_t n) { return hbn::norm(Limbs(w, w + n)); }
+// The context's ciphertext words as a compile-time L: f(std::integral_constant<int, L>) for
+// L = c->L2 in {256, 128, 64}, at most MaxL (an OU context has 64 or 128 words, and no TPI-8 OU
+// kernel exists).  Every entry point states its argument list once, inside f.
+template <int MaxL = 256, class F>
+auto with_limbs(const fphe_ctx* c, F&& f) {
+  if constexpr (MaxL >= 256)
+    if (c->L2 == 256) return f(std::integral_constant<int, 256>{});
+  if (c->L2 == 128) return f(std::integral_constant<int, 128>{});
+  return f(std::integral_constant<int, 64>{});
+}
 
-// little-endian 32-bit words -> nl limbs of lb bits (the engine radix of the modulus)
-Limbs to_radix(const Limbs& v, int nl, int lb) {
-  Limbs o((size_t)nl, 0u);
-  for (int i = 0; i < nl; ++i) {
-    const size_t bit = (size_t)lb * i, w = bit >> 5;
-    const unsigned off = (unsigned)(bit & 31);
-    u64 x = w < v.size() ? v[w] : 0u;
-    if (w + 1 < v.size()) x |= (u64)v[w + 1] << 32;
-    o[(size_t)i] = (u32)(x >> off) & ((1u << lb) - 1u);
+// Geometry of the reduced-radix engine at TPI lanes per element: E elements per wave, NL limbs
+// per element.  A launcher's kernels run on Engine<L> (n^2), Half<L> (n, p^2, q^2) or Small<L>
+// (p, q: the split key-holder modexp's first step).
+template <int TPI_>
+struct Geom {
+  static constexpr int TPI = TPI_, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  // dynamic LDS of a block whose waves keep `slot` words per element (the engine's own: NL)
+  static constexpr size_t lds(int slot = NL) { return (size_t)kWavesPerBlock * slot * E * 4; }
+  static constexpr size_t waves(size_t n) { return (n + E - 1) / E; }
+  // the window tables of `grid` blocks, `entries` per wave
+  static constexpr size_t table_bytes(unsigned grid, int entries) {
+    return (size_t)grid * kWavesPerBlock * entries * rad_ll(TPI) * FPHE_WAVE * 4;
   }
-  return o;
+};
+template <int L> using Engine = Geom<L / 32>;
+template <int L> using Half = Geom<L / 64>;
+template <int L> using Small = Geom<(L >= 128 ? L / 128 : 1)>;
+
+// the call's ChaCha20 key (zeros when the call has none and draws nothing)
+ChaChaKey chacha_key(const uint32_t key[8]) {
+  ChaChaKey ck{};
+  if (key)
+    for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
+  return ck;
 }
 
 template <typename KernT>
@@ -756,14 +738,34 @@ unsigned occ_grid(const fphe_ctx* c, KernT k, size_t lds, size_t waves, const ch
   return (unsigned)(g ? g : 1);
 }
 
-// Grid: `bpc` workgroups per CU (from LDS/VGPR budget), capped by the work.
-u32 ntiles_of(size_t count) { return (u32)((count + FPHE_WAVE - 1) / FPHE_WAVE); }
+template <typename KernT>
+void set_lds(KernT k, size_t bytes) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 
+// a kernel made ready to launch: its dynamic LDS allowed, and its grid for `waves` waves of work
+template <typename KernT>
+unsigned prep(const fphe_ctx* c, KernT k, size_t lds, size_t waves, const char* what) {
+  set_lds(k, lds);
+  return occ_grid(c, k, lds, waves, what);
+}
+
+u32 ntiles_of(size_t count) { return (u32)((count + FPHE_WAVE - 1) / FPHE_WAVE); }
+// bytes of a tile-major vector of `count` elements of `words` words
+size_t tile_bytes(size_t count, size_t words) { return (size_t)ntiles_of(count) * words * FPHE_WAVE * 4; }
+
+// Grid: `bpc` workgroups per CU (from LDS/VGPR budget), capped by the work.
 unsigned grid_for(const fphe_ctx* c, size_t count, int bpc) {
   const size_t groups = (count + kBlock - 1) / kBlock;  // 4 tiles per workgroup
   size_t g = (size_t)c->cus * bpc;
   if (groups < g) g = groups;
   return (unsigned)(g ? g : 1);
+}
+
+// grid of a one-thread-per-element kernel in blocks of 256: at most `per_cu` blocks per CU
+// (the r / (z_p, z_q) draws run 4, the codec and prep kernels 8)
+unsigned lane_grid(const fphe_ctx* c, size_t count, int per_cu) {
+  return (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * per_cu);
 }
 
 fphe_status ensure_scratch(fphe_ctx* c, size_t bytes, hipStream_t s) {
@@ -793,9 +795,31 @@ size_t span_elems(const fphe_ctx* c, KernT k, size_t lds, int E) {
   return cap * rounds;  // a multiple of 64: spans start on tile boundaries
 }
 
-template <typename KernT>
-void set_lds(KernT k, size_t bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// A call's spans under its leading kernel k (on engine G): elements per span, elements of the
+// first (the largest) span, which sizes the scratch, and k's grid for it.
+struct Spans {
+  size_t span, m0;
+  unsigned grid;
+};
+template <class G, typename KernT>
+Spans prep_spans(const fphe_ctx* c, KernT k, size_t lds, size_t count, const char* what) {
+  set_lds(k, lds);
+  Spans sp;
+  sp.span = span_elems(c, k, lds, G::E);
+  sp.m0 = count < sp.span ? count : sp.span;
+  sp.grid = occ_grid(c, k, lds, G::waves(sp.m0), what);
+  return sp;
+}
+
+// f(e0, m, t0) for each span in turn (they run in stream order over one scratch): m elements
+// from element e0, whose tile is t0.  Stops at the first span that fails.
+template <class F>
+fphe_status for_spans(size_t count, size_t span, F&& f) {
+  for (size_t e0 = 0; e0 < count; e0 += span) {
+    const fphe_status st = f(e0, count - e0 < span ? count - e0 : span, e0 / FPHE_WAVE);
+    if (st != FPHE_OK) return st;
+  }
+  return FPHE_OK;
 }
 
 // workgroups per CU for a kernel whose per-wave LDS slot is `slot_limbs` limbs
@@ -805,19 +829,14 @@ int bpc_for_slot(int slot_limbs) {
   return b < 1 ? 1 : (b > 2 ? 2 : b);
 }
 
-}  // namespace
-
-namespace {
 // ---- reduced-radix engine launchers (kernels27.h) ---------------------------------------
 template <int L>
 fphe_status launch_mont_const27(fphe_ctx* c, const uint32_t* C, size_t count, const u32* X, uint32_t* Co,
                                 hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = KS<TPI>::template mont_const<L>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const unsigned grid = occ_grid(c, kern, lds, (count + E - 1) / E, "mont_const27");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, C, count, X, Co, (u32)NL);
+  using G = Engine<L>;
+  auto kern = KS<G::TPI>::template mont_const<L>();
+  const unsigned grid = prep(c, kern, G::lds(), G::waves(count), "mont_const27");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, C, count, X, Co, (u32)G::NL);
   return hip_ok(hipGetLastError());
 }
 
@@ -825,92 +844,74 @@ template <int L>
 fphe_status launch_encrypt27(fphe_ctx* c, const uint32_t* P, uint32_t lp, const uint8_t* neg, size_t count, int obf,
                              const uint32_t* r, const uint32_t key[8], uint64_t nonce, uint32_t* C, uint8_t* sign,
                              hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, LDSW = NL > L + 3 ? NL : L + 3, L1 = L / 2;
-  auto kern = KS<TPI>::template encrypt<L, kWinSlide>();
-  const size_t lds = (size_t)kWavesPerBlock * LDSW * E * 4;
-  set_lds(kern, lds);
-  const size_t span = span_elems(c, kern, lds, E);
-  const size_t m0 = count < span ? count : span;
-  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "encrypt27");
-  const size_t tbytes = (size_t)grid * kWavesPerBlock * kTabEntries<kWinSlide> * rad_ll(TPI) * FPHE_WAVE * 4;
-  const size_t rbytes = (size_t)ntiles_of(m0) * L1 * FPHE_WAVE * 4;
+  using G = Engine<L>;
+  constexpr int LDSW = G::NL > L + 3 ? G::NL : L + 3, L1 = L / 2;
+  auto kern = KS<G::TPI>::template encrypt<L, kWinSlide>();
+  const size_t lds = G::lds(LDSW);
+  const Spans sp = prep_spans<G>(c, kern, lds, count, "encrypt27");
+  const size_t tbytes = G::table_bytes(sp.grid, kTabEntries<kWinSlide>);
   const bool draw = obf && !r;
-  ChaChaKey ck;
-  if (draw)
-    for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
+  const ChaChaKey ck = chacha_key(draw ? key : nullptr);
   if (obf && (int64_t)count <= c->wide_encrypt_max) {
     // few elements: one wave per element on the latency kernel (wide_dev.h), M-form written
     // directly; r drawn as on the throughput path (element e's stream), so the integers agree
-    const size_t rb = (size_t)ntiles_of(count) * L1 * FPHE_WAVE * 4;
-    if (draw && ensure_scratch(c, rb, s) != FPHE_OK) return FPHE_ERR_HIP;
+    if (draw && ensure_scratch(c, tile_bytes(count, L1), s) != FPHE_OK) return FPHE_ERR_HIP;
     const u32* rbuf = r;
     if (draw) {
-      const unsigned rgrid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 4);
-      hipLaunchKernelGGL(k_draw_r<L1>, dim3(rgrid), dim3(256), 0, s, c->K, count, ck, nonce, (size_t)0, c->scratch);
+      hipLaunchKernelGGL(k_draw_r<L1>, dim3(lane_grid(c, count, 4)), dim3(256), 0, s, c->K, count, ck, nonce, (size_t)0,
+                         c->scratch);
       rbuf = c->scratch;
     }
     hipLaunchKernelGGL((k_encrypt_wide<L, kWinSlide>), dim3((unsigned)count), dim3(64), 0, s, c->K, P, lp, neg, count,
                        rbuf, C, sign);
     return hip_ok(hipGetLastError());
   }
-  if (ensure_scratch(c, tbytes + (draw ? rbytes : 0), s) != FPHE_OK) return FPHE_ERR_HIP;
-  for (size_t e0 = 0; e0 < count; e0 += span) {  // spans run in stream order over one scratch
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
+  if (ensure_scratch(c, tbytes + (draw ? tile_bytes(sp.m0, L1) : 0), s) != FPHE_OK) return FPHE_ERR_HIP;
+  return for_spans(count, sp.span, [&](size_t e0, size_t m, size_t t0) {
     const u32* rbuf = r ? r + t0 * L1 * FPHE_WAVE : nullptr;
     if (draw) {
       u32* rdev = c->scratch + tbytes / 4;
-      const unsigned rgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 4);
-      hipLaunchKernelGGL(k_draw_r<L1>, dim3(rgrid), dim3(256), 0, s, c->K, m, ck, nonce, e0, rdev);
+      hipLaunchKernelGGL(k_draw_r<L1>, dim3(lane_grid(c, m, 4)), dim3(256), 0, s, c->K, m, ck, nonce, e0, rdev);
       rbuf = rdev;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, P + t0 * lp * FPHE_WAVE, lp, neg + e0, m, obf,
+    hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kBlock), lds, s, c->K, P + t0 * lp * FPHE_WAVE, lp, neg + e0, m, obf,
                        rbuf, C + t0 * L * FPHE_WAVE, sign + e0, c->scratch, (u32)LDSW);
     // into the Montgomery-resident form, in place (one product per element)
-    if (launch_mont_const27<L>(c, C + t0 * L * FPHE_WAVE, m, c->K.N2R2_27, C + t0 * L * FPHE_WAVE, s) != FPHE_OK)
-      return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
+    return launch_mont_const27<L>(c, C + t0 * L * FPHE_WAVE, m, c->K.N2R2_27, C + t0 * L * FPHE_WAVE, s);
+  });
 }
 
 template <int L>
 fphe_status launch_decrypt27(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, hipStream_t s) {
-  constexpr int TPI = L / 64, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, LH = L / 2, LQ = L / 4;
+  using G = Half<L>;
+  constexpr int LH = L / 2, LQ = L / 4, W = kWinDec<G::TPI>;
+  const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;  // of the CRT tail
   if ((int64_t)count <= c->wide_decrypt_max) {
     // few elements: one wave per (element, half) on the latency kernel (wide_dev.h), which
     // writes the same y_s rows k_pow_half27 does; the CRT tail is the same kernel
-    const size_t ybytes = (size_t)ntiles_of(count) * 2 * LH * FPHE_WAVE * 4;
-    if (ensure_scratch(c, ybytes, s) != FPHE_OK) return FPHE_ERR_HIP;
+    if (ensure_scratch(c, tile_bytes(count, 2 * LH), s) != FPHE_OK) return FPHE_ERR_HIP;
     u32* Y = c->scratch;
-    hipLaunchKernelGGL((k_pow_half_wide<L, kWinDec<TPI>>), dim3((unsigned)(2 * count)), dim3(64), 0, s, c->K, C, count, Y);
+    hipLaunchKernelGGL((k_pow_half_wide<L, W>), dim3((unsigned)(2 * count)), dim3(64), 0, s, c->K, C, count, Y);
     auto kcrt = k_decrypt_crt<L>;
-    const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;
     set_lds(kcrt, lds2);
     hipLaunchKernelGGL(kcrt, dim3(grid_for(c, count, bpc_for_slot(LQ))), dim3(kBlock), lds2, s, c->K, Y,
                        ntiles_of(count), P);
     return hip_ok(hipGetLastError());
   }
-  auto kern = KS<TPI>::template pow_half<L, kWinDec<TPI>, false>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const size_t span = span_elems(c, kern, lds, E);
-  const size_t m0 = count < span ? count : span;
-  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "decrypt_pow27");
-  const size_t tbytes = (size_t)grid * kWavesPerBlock * kTabEntries<kWinDec<TPI>> * rad_ll(TPI) * FPHE_WAVE * 4;
-  const size_t ybytes = (size_t)ntiles_of(m0) * 2 * LH * FPHE_WAVE * 4;
-  if (ensure_scratch(c, tbytes + ybytes, s) != FPHE_OK) return FPHE_ERR_HIP;
+  auto kern = KS<G::TPI>::template pow_half<L, W, false>();
+  const Spans sp = prep_spans<G>(c, kern, G::lds(), count, "decrypt_pow27");
+  const size_t tbytes = G::table_bytes(sp.grid, kTabEntries<W>);
+  if (ensure_scratch(c, tbytes + tile_bytes(sp.m0, 2 * LH), s) != FPHE_OK) return FPHE_ERR_HIP;
   u32* Y = c->scratch + tbytes / 4;
   auto kcrt = k_decrypt_crt<L>;
-  const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;
   set_lds(kcrt, lds2);
-  for (size_t e0 = 0; e0 < count; e0 += span) {
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, C + t0 * L * FPHE_WAVE, m, Y, c->scratch,
-                       (u32)NL);
-    const unsigned grid2 = grid_for(c, m, bpc_for_slot(LQ));
-    hipLaunchKernelGGL(kcrt, dim3(grid2), dim3(kBlock), lds2, s, c->K, Y, ntiles_of(m), P + t0 * LH * FPHE_WAVE);
-    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
+  return for_spans(count, sp.span, [&](size_t, size_t m, size_t t0) {
+    hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kBlock), G::lds(), s, c->K, C + t0 * L * FPHE_WAVE, m, Y, c->scratch,
+                       (u32)G::NL);
+    hipLaunchKernelGGL(kcrt, dim3(grid_for(c, m, bpc_for_slot(LQ))), dim3(kBlock), lds2, s, c->K, Y, ntiles_of(m),
+                       P + t0 * LH * FPHE_WAVE);
+    return hip_ok(hipGetLastError());
+  });
 }
 
 // key-holder encryption: r^n mod p^2 and mod q^2 (half-size modexps), then the CRT
@@ -919,111 +920,78 @@ template <int L>
 fphe_status launch_encrypt_crt27(fphe_ctx* c, const uint32_t* P, uint32_t lp, const uint8_t* neg, size_t count,
                                  const uint32_t* r, const uint32_t key[8], uint64_t nonce, uint32_t* C,
                                  uint8_t* sign, hipStream_t s) {
-  constexpr int TPIh = L / 64, Eh = FPHE_WAVE / TPIh, NLh = rad_ll(TPIh) * TPIh, L1 = L / 2;
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, LDSW = NL > L + 3 ? NL : L + 3;
-  constexpr int TPIs = L >= 128 ? L / 128 : 1, Es = FPHE_WAVE / TPIs, NLs = rad_ll(TPIs) * TPIs;
-  auto k1 = KS<TPIh>::template pow_half<L, kWinSlide, true>();
-  const size_t lds1 = (size_t)kWavesPerBlock * NLh * Eh * 4;
-  set_lds(k1, lds1);
-  const size_t span = span_elems(c, k1, lds1, Eh);
-  const size_t m0 = count < span ? count : span;
-  const unsigned g1 = occ_grid(c, k1, lds1, (m0 + Eh - 1) / Eh, "pow_half27<enc>");
-  size_t tbytes = (size_t)g1 * kWavesPerBlock * kTabEntries<kWinSlide> * rad_ll(TPIh) * FPHE_WAVE * 4;
+  using G = Engine<L>;
+  using Gh = Half<L>;
+  using Gs = Small<L>;
+  constexpr int L1 = L / 2, LDSW = G::NL > L + 3 ? G::NL : L + 3;
+  auto k1 = KS<Gh::TPI>::template pow_half<L, kWinSlide, true>();
+  const Spans sp = prep_spans<Gh>(c, k1, Gh::lds(), count, "pow_half27<enc>");
+  const unsigned g1 = sp.grid;
+  size_t tbytes = Gh::table_bytes(g1, kTabEntries<kWinSlide>);
   // the split modexp's first step (FPHE_KH_SPLIT): z_s = r^(e_s) mod s into Z, then k1 raises
   // z_s to s mod s^2; both share the window-table region
-  auto k0 = KS<TPIs>::template pow_small<L, kWinSlide>();
-  const size_t lds0 = (size_t)kWavesPerBlock * NLs * Es * 4;
+  auto k0 = KS<Gs::TPI>::template pow_small<L, kWinSlide>();
   unsigned g0 = 0;
   size_t zbytes = 0;
   const bool direct = !r && c->kh_direct && c->kh_direct_z;
   if (kKhSplit<L> && !direct) {  // the direct draw skips the first step (and its table)
-    set_lds(k0, lds0);
-    g0 = occ_grid(c, k0, lds0, (m0 + Es - 1) / Es, "pow_small27");
-    tbytes = std::max(tbytes, (size_t)g0 * kWavesPerBlock * kTabEntries<kWinSlide> * rad_ll(TPIs) * FPHE_WAVE * 4);
+    g0 = prep(c, k0, Gs::lds(), Gs::waves(sp.m0), "pow_small27");
+    tbytes = std::max(tbytes, Gs::table_bytes(g0, kTabEntries<kWinSlide>));
   }
-  if (kKhSplit<L> || direct) zbytes = (size_t)ntiles_of(m0) * 2 * kZWords<L> * FPHE_WAVE * 4;
+  if (kKhSplit<L> || direct) zbytes = tile_bytes(sp.m0, 2 * kZWords<L>);
   // the second step alone on drawn (z_p, z_q): k1 itself when the key splits its modexp,
   // otherwise (keys <= 1024 bits) the same kernel reading Z (|p|-bit exponent in place of |n|)
-  auto k1z = KS<TPIh>::template pow_half_z<L, kWinSlide>();
-  if (direct && !kKhSplit<L>) set_lds(k1z, lds1);
-  const size_t ybytes = (size_t)ntiles_of(m0) * 2 * L1 * FPHE_WAVE * 4;
-  const size_t rbytes = (size_t)ntiles_of(m0) * L1 * FPHE_WAVE * 4;
-  if (ensure_scratch(c, tbytes + ybytes + zbytes + ((r || direct) ? 0 : rbytes), s) != FPHE_OK) return FPHE_ERR_HIP;
+  auto k1z = KS<Gh::TPI>::template pow_half_z<L, kWinSlide>();
+  if (direct && !kKhSplit<L>) set_lds(k1z, Gh::lds());
+  const size_t ybytes = tile_bytes(sp.m0, 2 * L1);
+  if (ensure_scratch(c, tbytes + ybytes + zbytes + ((r || direct) ? 0 : tile_bytes(sp.m0, L1)), s) != FPHE_OK)
+    return FPHE_ERR_HIP;
   u32* Y = c->scratch + tbytes / 4;
   u32* Z = Y + ybytes / 4;
-  ChaChaKey ck;
-  if (!r)
-    for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
-  auto k2 = KS<TPI>::template encrypt_crt<L>();
-  const size_t lds2 = (size_t)kWavesPerBlock * LDSW * E * 4;
-  set_lds(k2, lds2);
-  const unsigned g2 = occ_grid(c, k2, lds2, (m0 + E - 1) / E, "encrypt_crt27");
-  for (size_t e0 = 0; e0 < count; e0 += span) {
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
+  const ChaChaKey ck = chacha_key(r ? nullptr : key);
+  auto k2 = KS<G::TPI>::template encrypt_crt<L>();
+  const size_t lds2 = G::lds(LDSW);
+  const unsigned g2 = prep(c, k2, lds2, G::waves(sp.m0), "encrypt_crt27");
+  return for_spans(count, sp.span, [&](size_t e0, size_t m, size_t t0) {
     const u32* rbuf = r ? r + t0 * L1 * FPHE_WAVE : nullptr;
-    const unsigned rgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 4);
     if (direct) {  // (z_p, z_q) drawn in place of r and its first modexp step
-      hipLaunchKernelGGL(k_draw_z<L>, dim3(rgrid), dim3(256), 0, s, c->K, m, ck, nonce, e0, Z);
+      hipLaunchKernelGGL(k_draw_z<L>, dim3(lane_grid(c, m, 4)), dim3(256), 0, s, c->K, m, ck, nonce, e0, Z);
       if ((int64_t)count <= c->wide_kh_encrypt_max)  // few elements: one per wave and half
-        hipLaunchKernelGGL((k_pow_half_enc_wide<L, kWinDec<TPIh>>), dim3((unsigned)(2 * m)), dim3(64), 0, s, c->K,
+        hipLaunchKernelGGL((k_pow_half_enc_wide<L, kWinDec<Gh::TPI>>), dim3((unsigned)(2 * m)), dim3(64), 0, s, c->K,
                            (const u32*)Z, m, Y);
       else
-        hipLaunchKernelGGL(k1z, dim3(g1), dim3(kBlock), lds1, s, c->K, (const u32*)Z, m, Y, c->scratch, (u32)NLh);
-      hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), lds2, s, c->K, P + t0 * lp * FPHE_WAVE, lp, neg + e0, m, Y,
-                         C + t0 * L * FPHE_WAVE, sign + e0, (u32)LDSW);
-      if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-      continue;
-    }
-    if (!r) {
-      u32* rdev = Z + zbytes / 4;
-      hipLaunchKernelGGL(k_draw_r<L1>, dim3(rgrid), dim3(256), 0, s, c->K, m, ck, nonce, e0, rdev);
-      rbuf = rdev;
-    }
-    if (kKhSplit<L>) {
-      hipLaunchKernelGGL(k0, dim3(g0), dim3(kBlock), lds0, s, c->K, rbuf, m, Z, c->scratch, (u32)NLs);
-      hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), lds1, s, c->K, (const u32*)Z, m, Y, c->scratch, (u32)NLh);
+        hipLaunchKernelGGL(k1z, dim3(g1), dim3(kBlock), Gh::lds(), s, c->K, (const u32*)Z, m, Y, c->scratch,
+                           (u32)Gh::NL);
     } else {
-      hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), lds1, s, c->K, rbuf, m, Y, c->scratch, (u32)NLh);
+      if (!r) {
+        u32* rdev = Z + zbytes / 4;
+        hipLaunchKernelGGL(k_draw_r<L1>, dim3(lane_grid(c, m, 4)), dim3(256), 0, s, c->K, m, ck, nonce, e0, rdev);
+        rbuf = rdev;
+      }
+      if (kKhSplit<L>) {
+        hipLaunchKernelGGL(k0, dim3(g0), dim3(kBlock), Gs::lds(), s, c->K, rbuf, m, Z, c->scratch, (u32)Gs::NL);
+        hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), Gh::lds(), s, c->K, (const u32*)Z, m, Y, c->scratch,
+                           (u32)Gh::NL);
+      } else {
+        hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), Gh::lds(), s, c->K, rbuf, m, Y, c->scratch, (u32)Gh::NL);
+      }
     }
     hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), lds2, s, c->K, P + t0 * lp * FPHE_WAVE, lp, neg + e0, m, Y,
                        C + t0 * L * FPHE_WAVE, sign + e0, (u32)LDSW);
-    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
+    return hip_ok(hipGetLastError());
+  });
 }
 
 template <int L>
 fphe_status launch_fold27(fphe_ctx* c, const uint32_t* Src, const uint8_t* ssign, const int32_t* sexp,
                           const int64_t* ord, const int64_t* cstart, const int32_t* clen, size_t nchunks,
                           uint32_t* Co, uint8_t* so, int32_t* eo, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = KS<TPI>::template fold<L, int64_t, false, true>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const unsigned grid = occ_grid(c, kern, lds, (nchunks + E - 1) / E, "fold27");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Src, ssign, sexp, ord, cstart, clen, nchunks,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, (u32*)nullptr, Co, so, eo, (u32)NL);
+  using G = Engine<L>;
+  auto kern = KS<G::TPI>::template fold<L, int64_t, false, true>();
+  const unsigned grid = prep(c, kern, G::lds(), G::waves(nchunks), "fold27");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, Src, ssign, sexp, ord, cstart, clen, nchunks,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, (u32*)nullptr, Co, so, eo, (u32)G::NL);
   return hip_ok(hipGetLastError());
-}
-
-// ---- SecureBoost bin indexes -> fold terms (fphe_positions_terms) ---------------------------
-// positions [ns][npos] (int32 or int64, sample-major as iupdate's Vec<Vec<usize>>): term
-// (i, j, t) = pair p = i npos + j, then t < stride, at p stride + t: src = i stride + t, slot =
-// pos stride + t, or -1 when pos is outside [0, lim) (fphe_fold_segments then reports the
-// segment out of range).  One thread per pair; the range test runs on the position's own width.
-template <typename PT>
-__global__ __launch_bounds__(256) void k_positions_terms(const PT* __restrict__ pos, size_t npairs, uint32_t npos,
-                                                          int32_t stride, int64_t lim, int32_t* __restrict__ src,
-                                                          int32_t* __restrict__ slot) {
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < npairs; p += (size_t)gridDim.x * blockDim.x) {
-    const int64_t v = (int64_t)pos[p];
-    const bool ok = v >= 0 && v < lim;
-    const int32_t i = (int32_t)(p / npos);
-    for (int32_t t = 0; t < stride; ++t) {
-      src[p * stride + t] = i * stride + t;
-      slot[p * stride + t] = ok ? (int32_t)v * stride + t : -1;
-    }
-  }
 }
 
 // ---- segmented fold with device grouping (fphe_fold_segments) --------------------------------
@@ -1149,7 +1117,7 @@ struct FoldOut {
 // stats (may be null): the first level reads back {largest run, non-empty keys}
 template <int L>
 fphe_status fold_level(fphe_ctx* c, FoldLevel& in, FoldOut& out, CallBufs& B, bool read_stats) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  using G = Engine<L>;
   hipStream_t s = B.s;
   const int32_t k = fold_klen(in.n_ub);
   int32_t* nch = B.get<int32_t>(in.nkeys);
@@ -1201,14 +1169,12 @@ fphe_status fold_level(fphe_ctx* c, FoldLevel& in, FoldOut& out, CallBufs& B, bo
     hipLaunchKernelGGL(k_gr_perm, dim3(gk), dim3(kGrBlock), 0, s, in.cnt, choff, nfull, fulloff, nf, boff, bfill,
                        in.nkeys, k, cperm);
   }
-  auto kern = in.ord ? KS<TPI>::template fold<L, int32_t, true, true>()
-                     : KS<TPI>::template fold<L, int32_t, true, false>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const unsigned grid = occ_grid(c, kern, lds, (ub + E - 1) / E, "fold_segments");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, in.rows, in.sign, in.exp, in.ord, cstart, clen,
-                     ub, (const int32_t*)(hdr + 2), (const int32_t*)cperm, ctr, out.rows, out.sign, out.exp,
-                     (u32)NL);
+  auto kern = in.ord ? KS<G::TPI>::template fold<L, int32_t, true, true>()
+                     : KS<G::TPI>::template fold<L, int32_t, true, false>();
+  const unsigned grid = prep(c, kern, G::lds(), G::waves(ub), "fold_segments");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, in.rows, in.sign, in.exp, in.ord, cstart,
+                     clen, ub, (const int32_t*)(hdr + 2), (const int32_t*)cperm, ctr, out.rows, out.sign, out.exp,
+                     (u32)G::NL);
   out.cnt = nch;
   out.off = choff;
   out.n_dev = hdr + 2;
@@ -1223,7 +1189,7 @@ fphe_status fold_level(fphe_ctx* c, FoldLevel& in, FoldOut& out, CallBufs& B, bo
 // in.nnz of them, the exact count on the device).
 template <int L>
 fphe_status fold_keys_tree(fphe_ctx* c, const FoldLevel& in, FoldOut& out, CallBufs& B) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  using G = Engine<L>;
   hipStream_t s = B.s;
   int32_t* flag = B.get<int32_t>(in.nkeys);
   int32_t* pos = B.get<int32_t>(in.nkeys);
@@ -1243,12 +1209,11 @@ fphe_status fold_keys_tree(fphe_ctx* c, const FoldLevel& in, FoldOut& out, CallB
   if (!B.ok) return FPHE_ERR_HIP;
   hipLaunchKernelGGL(k_gr_keyof, dim3(gr_grid(in.nkeys, c->cus)), dim3(kGrBlock), 0, s, (const int32_t*)flag,
                      (const int32_t*)pos, in.nkeys, keyof);
-  auto kern = KS<TPI>::template keytree<L>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const unsigned grid = occ_grid(c, kern, lds, ub, "keytree");  // a wave per non-empty key (bound)
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, in.rows, in.sign, in.exp, in.cnt, in.off,
-                     (const int32_t*)keyof, (const int32_t*)(hdr + 2), out.rows, out.sign, out.exp, out.key, (u32)NL);
+  auto kern = KS<G::TPI>::template keytree<L>();
+  const unsigned grid = prep(c, kern, G::lds(), ub, "keytree");  // a wave per non-empty key (bound)
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, in.rows, in.sign, in.exp, in.cnt, in.off,
+                     (const int32_t*)keyof, (const int32_t*)(hdr + 2), out.rows, out.sign, out.exp, out.key,
+                     (u32)G::NL);
   out.cnt = flag;
   out.off = pos;
   out.n_dev = hdr + 2;
@@ -1281,7 +1246,8 @@ template <int L>
 fphe_status launch_fold_segments(fphe_ctx* c, const u32* Src, const u8* ssign, const int32_t* sexp, size_t nsrc,
                                  const int32_t* idx, const int32_t* seg, size_t T, size_t nseg, u32* Co, u8* so,
                                  int32_t* eo, u8* present, int32_t* err, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  using G = Engine<L>;
+  constexpr int E = G::E;
   CallBufs B(s);
   const unsigned g0 = gr_grid(nseg * FPHE_WAVE, c->cus);
   hipLaunchKernelGGL(k_gr_init_out<L>, dim3(g0), dim3(kGrBlock), 0, s, nseg, c->K.N2M1, Co, so, eo, present);
@@ -1363,10 +1329,9 @@ fphe_status launch_fold_segments(fphe_ctx* c, const u32* Src, const u8* ssign, c
   // 4. fold every (segment, exponent) run to one partial.  First level: the sorted items in
   // equal ranges of r per wave slot, whatever the runs (k_segfold27: balanced, a whole number
   // of wave rounds); then chunk levels per key until one partial is left per key.
-  auto ksf = KS<TPI>::template segfold<L, true>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(ksf, lds);
-  const size_t round = (size_t)occ_grid(c, ksf, lds, (size_t)1 << 40, "segfold") * kWavesPerBlock * E;
+  auto ksf = KS<G::TPI>::template segfold<L, true>();
+  const size_t lds = G::lds();
+  const size_t round = (size_t)prep(c, ksf, lds, (size_t)1 << 40, "segfold") * kWavesPerBlock * E;
   size_t r = (T + round - 1) / round;
   r = r < 8 ? 8 : (r > (size_t)kSegFoldMax ? (size_t)kSegFoldMax : r);
   size_t nslots = (T + r - 1) / r;
@@ -1445,9 +1410,9 @@ fphe_status launch_fold_segments(fphe_ctx* c, const u32* Src, const u8* ssign, c
   P.exp = B.get<int32_t>(ub1);
   P.key = B.get<int32_t>(ub1);
   if (!B.ok || sj.join() != FPHE_OK) return FPHE_ERR_HIP;
-  hipLaunchKernelGGL(ksf, dim3(occ_grid(c, ksf, lds, (nslots + E - 1) / E, "segfold")), dim3(kBlock), lds, s, c->K,
+  hipLaunchKernelGGL(ksf, dim3(occ_grid(c, ksf, lds, G::waves(nslots), "segfold")), dim3(kBlock), lds, s, c->K,
                      rows, emin, (int32_t)NE, ord, skey, T, (u32)r, (const int32_t*)plan, poff, P.rows, P.sign, P.exp, P.key,
-                     (u32)NL);
+                     (u32)G::NL);
   P.cnt = cnt2;
   P.off = off2;
   P.n_dev = hdr + 2;
@@ -1494,11 +1459,10 @@ fphe_status launch_fold_segments(fphe_ctx* c, const u32* Src, const u8* ssign, c
     hipLaunchKernelGGL(k_gr_gapkeys, dim3(gp), dim3(kGrBlock), 0, s, gap, P.n_dev, (int32_t)(NE - 1), gk, gc);
     if (dev_scan(c, gc, ng, go, nullptr, B) != FPHE_OK) return FPHE_ERR_HIP;
     hipLaunchKernelGGL(k_gr_scatter_n, dim3(gp), dim3(kGrBlock), 0, s, gk, P.n_dev, go, gf, gord);
-    auto ka = KS<TPI>::template align_rows<L>();
-    set_lds(ka, lds);
-    const unsigned ga = occ_grid(c, ka, lds, (np + E - 1) / E, "align_rows");
+    auto ka = KS<G::TPI>::template align_rows<L>();
+    const unsigned ga = prep(c, ka, lds, G::waves(np), "align_rows");
     hipLaunchKernelGGL(ka, dim3(ga), dim3(kBlock), lds, s, c->K, P.rows, P.sign, gap, gord, P.n_dev, tile_ctr,
-                       (u32)NL);
+                       (u32)G::NL);
     // the partials are in (segment, exponent) order: contiguous per segment
     if (dev_scan(c, scnt, nseg, soff, nullptr, B) != FPHE_OK) return FPHE_ERR_HIP;
     FoldOut Q{};
@@ -1526,10 +1490,9 @@ template <int L>
 fphe_status launch_add27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, const int32_t* ea, const uint32_t* Cb,
                          const uint8_t* sb, const int32_t* eb, int bstride, size_t count, const int32_t* ord,
                          uint32_t* Co, uint8_t* so, int32_t* eo, int32_t* err, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = KS<TPI>::template add<L>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
+  using G = Engine<L>;
+  auto kern = KS<G::TPI>::template add<L>();
+  set_lds(kern, G::lds());
   const size_t cmax = add_max_count(L);
   if (ord && count > cmax) return FPHE_ERR_ARG;  // an order must stay inside one addressable chunk
   if (count == 0) return FPHE_OK;
@@ -1541,12 +1504,12 @@ fphe_status launch_add27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, con
     const size_t n = count - s0 < cmax ? count - s0 : cmax;
     const size_t wo = s0 / FPHE_WAVE * L * FPHE_WAVE;  // word offset of the chunk's first tile
     // a multiple of kAddRegions blocks: every run of wave tiles has its own blocks
-    const unsigned g0 = occ_grid(c, kern, lds, (n + E - 1) / E, "add27");
+    const unsigned g0 = occ_grid(c, kern, G::lds(), G::waves(n), "add27");
     const unsigned grid = (g0 + kAddRegions - 1) / kAddRegions * kAddRegions;
     if (hipMemsetAsync(next_tile, 0, kCtrBytes, s) != hipSuccess) return FPHE_ERR_HIP;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Ca + wo, sa + s0, ea + s0,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, Ca + wo, sa + s0, ea + s0,
                        bstride ? Cb + wo : Cb, bstride ? sb + s0 : sb, bstride ? eb + s0 : eb, bstride, n, ord,
-                       Co + wo, so + s0, eo + s0, err, next_tile, (u32)NL);
+                       Co + wo, so + s0, eo + s0, err, next_tile, (u32)G::NL);
   }
   return hip_ok(hipGetLastError());
 }
@@ -1554,26 +1517,24 @@ fphe_status launch_add27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, con
 template <int L>
 fphe_status launch_sqmul27(fphe_ctx* c, const uint32_t* Ca, const uint32_t* Cb, const uint8_t* sb, int nsq,
                            size_t count, uint32_t* Co, uint8_t* so, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = KS<TPI>::template sqmul<L>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const unsigned grid = occ_grid(c, kern, lds, (count + E - 1) / E, "sqmul27");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Ca, Cb, sb, nsq, count, Co, so, (u32)NL);
+  using G = Engine<L>;
+  auto kern = KS<G::TPI>::template sqmul<L>();
+  const unsigned grid = prep(c, kern, G::lds(), G::waves(count), "sqmul27");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, Ca, Cb, sb, nsq, count, Co, so, (u32)G::NL);
   return hip_ok(hipGetLastError());
 }
 
 template <int L>
 fphe_status launch_align27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, const int32_t* gap, size_t count,
                            uint32_t* Co, uint8_t* so, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = KS<TPI>::template align<L>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
+  using G = Engine<L>;
+  auto kern = KS<G::TPI>::template align<L>();
+  set_lds(kern, G::lds());
   if (ensure_scratch(c, 256, s) != FPHE_OK) return FPHE_ERR_HIP;  // the wave-tile counter
   if (hipMemsetAsync(c->scratch, 0, sizeof(u32), s) != hipSuccess) return FPHE_ERR_HIP;
-  const unsigned grid = occ_grid(c, kern, lds, (count + E - 1) / E, "align27");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Ca, sa, gap, count, Co, so, c->scratch, (u32)NL);
+  const unsigned grid = occ_grid(c, kern, G::lds(), G::waves(count), "align27");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), G::lds(), s, c->K, Ca, sa, gap, count, Co, so, c->scratch,
+                     (u32)G::NL);
   return hip_ok(hipGetLastError());
 }
 
@@ -1581,29 +1542,22 @@ fphe_status launch_align27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, c
 template <int L>
 void launch_inv27(fphe_ctx* c, const uint32_t* Ca, size_t count, const uint8_t* need, uint32_t* Co,
                   int32_t* err, u32* X0, hipStream_t s) {
-  constexpr int TPIh = L / 64, Eh = FPHE_WAVE / TPIh, NLh = rad_ll(TPIh) * TPIh, L1 = L / 2;
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
+  using G = Engine<L>;
+  using Gh = Half<L>;
   if constexpr (L <= 128) {
     if (c->ou) {  // n = p^2 q: one full-width safegcd (ou_dev.h), no lift
-      auto ko = OU<TPI>::template inv<L>();
-      const size_t ldso = (size_t)kWavesPerBlock * NL * E * 4;
-      set_lds(ko, ldso);
-      const unsigned go = occ_grid(c, ko, ldso, (count + E - 1) / E, "ou_inv27");
-      hipLaunchKernelGGL(ko, dim3(go), dim3(kBlock), ldso, s, c->K, Ca, count, need, Co, err, (u32)NL);
+      auto ko = OU<G::TPI>::template inv<L>();
+      const unsigned go = prep(c, ko, G::lds(), G::waves(count), "ou_inv27");
+      hipLaunchKernelGGL(ko, dim3(go), dim3(kBlock), G::lds(), s, c->K, Ca, count, need, Co, err, (u32)G::NL);
       return;
     }
   }
-  auto k1 = KS<TPIh>::template inv_n<L>();
-  const size_t lds1 = (size_t)kWavesPerBlock * NLh * Eh * 4;
-  set_lds(k1, lds1);
-  const unsigned g1 = occ_grid(c, k1, lds1, (count + Eh - 1) / Eh, "inv_n27");
-  (void)L1;
-  hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), lds1, s, c->K, Ca, count, need, X0, err, (u32)NLh);
-  auto k2 = KS<TPI>::template inv_lift<L>();
-  const size_t lds2 = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(k2, lds2);
-  const unsigned g2 = occ_grid(c, k2, lds2, (count + E - 1) / E, "inv_lift27");
-  hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), lds2, s, c->K, Ca, count, need, X0, Co, (u32)NL);
+  auto k1 = KS<Gh::TPI>::template inv_n<L>();
+  const unsigned g1 = prep(c, k1, Gh::lds(), Gh::waves(count), "inv_n27");
+  hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), Gh::lds(), s, c->K, Ca, count, need, X0, err, (u32)Gh::NL);
+  auto k2 = KS<G::TPI>::template inv_lift<L>();
+  const unsigned g2 = prep(c, k2, G::lds(), G::waves(count), "inv_lift27");
+  hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), G::lds(), s, c->K, Ca, count, need, X0, Co, (u32)G::NL);
 }
 
 // Batch inversion mod n^2 (kernels27.h k_binv_pre27 / k_binv_post27): Co[e] = Ca[e]^-1 for
@@ -1612,10 +1566,10 @@ void launch_inv27(fphe_ctx* c, const uint32_t* Ca, size_t count, const uint8_t* 
 // inverse's mod-n intermediate.
 template <int L>
 size_t binv_scratch_bytes(size_t count) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, PER = FPHE_WAVE / E, KB = 4 * PER;
-  const size_t nwt = (ntiles_of(count) + 3) / 4, ntot = nwt * E;
-  return nwt * KB * rad_ll(TPI) * FPHE_WAVE * 4 + 2 * (size_t)ntiles_of(ntot) * L * FPHE_WAVE * 4 +
-         (size_t)ntiles_of(ntot) * (L / 2) * FPHE_WAVE * 4;
+  using G = Engine<L>;
+  constexpr int PER = FPHE_WAVE / G::E, KB = 4 * PER;
+  const size_t nwt = (ntiles_of(count) + 3) / 4, ntot = nwt * G::E;
+  return nwt * KB * rad_ll(G::TPI) * FPHE_WAVE * 4 + 2 * tile_bytes(ntot, L) + tile_bytes(ntot, L / 2);
 }
 
 // Vectors from this many elements invert by batches; shorter ones with one inverse each.
@@ -1627,24 +1581,22 @@ size_t binv_min() {
 template <int L>
 void launch_binv27(fphe_ctx* c, const uint32_t* Ca, size_t count, const uint8_t* need, uint32_t* Co, int32_t* err,
                    u32* W, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, PER = FPHE_WAVE / E, KB = 4 * PER;
-  const size_t nwt = (ntiles_of(count) + 3) / 4, ntot = nwt * E;
-  const size_t tab_words = nwt * KB * rad_ll(TPI) * FPHE_WAVE;
+  using G = Engine<L>;
+  constexpr int PER = FPHE_WAVE / G::E, KB = 4 * PER;
+  const size_t nwt = (ntiles_of(count) + 3) / 4, ntot = nwt * G::E;
+  const size_t tab_words = nwt * KB * rad_ll(G::TPI) * FPHE_WAVE;
   const size_t tot_words = (size_t)ntiles_of(ntot) * L * FPHE_WAVE;
   u32* Tab = W;
   u32* Tot = Tab + tab_words;
   u32* Inv = Tot + tot_words;
   u32* X0 = Inv + tot_words;
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  auto k1 = KS<TPI>::template binv_pre<L>();
-  set_lds(k1, lds);
-  const unsigned g1 = occ_grid(c, k1, lds, nwt, "binv_pre27");
-  hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), lds, s, c->K, Ca, count, need, Tab, Tot, (u32)NL);
+  auto k1 = KS<G::TPI>::template binv_pre<L>();
+  const unsigned g1 = prep(c, k1, G::lds(), nwt, "binv_pre27");
+  hipLaunchKernelGGL(k1, dim3(g1), dim3(kBlock), G::lds(), s, c->K, Ca, count, need, Tab, Tot, (u32)G::NL);
   launch_inv27<L>(c, Tot, ntot, nullptr, Inv, err, X0, s);
-  auto k2 = KS<TPI>::template binv_post<L>();
-  set_lds(k2, lds);
-  const unsigned g2 = occ_grid(c, k2, lds, nwt, "binv_post27");
-  hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), lds, s, c->K, Ca, count, need, Tab, Inv, Co, (u32)NL);
+  auto k2 = KS<G::TPI>::template binv_post<L>();
+  const unsigned g2 = prep(c, k2, G::lds(), nwt, "binv_post27");
+  hipLaunchKernelGGL(k2, dim3(g2), dim3(kBlock), G::lds(), s, c->K, Ca, count, need, Tab, Inv, Co, (u32)G::NL);
 }
 
 template <int L>
@@ -1652,34 +1604,30 @@ fphe_status launch_mul27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, con
                          uint32_t lp, const uint8_t* pneg, const int32_t* pexp, int pstride, size_t count,
                          uint32_t* Co, uint8_t* so, int32_t* eo, int32_t* err, hipStream_t s) {
   (void)sa;  // powm results are canonical whatever the base's sign (lib.rs:334-349)
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, L1 = L / 2;
-  auto kern = KS<TPI>::template mul<L, kWinMul>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
+  using G = Engine<L>;
+  constexpr int L1 = L / 2;
+  auto kern = KS<G::TPI>::template mul<L, kWinMul>();
   // spans as for encrypt: plaintexts that are encoded negative ints take k-bit exponents
-  const size_t span = span_elems(c, kern, lds, E);
-  const size_t m0 = count < span ? count : span;
-  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "mul27");
+  const Spans sp = prep_spans<G>(c, kern, G::lds(), count, "mul27");
   // scratch: [window tables][need T*64 B][ebits T*64 i32][E T*L1*64 w][Cinv T*L*64 w][X0 T*L1*64 w]
-  const size_t nt = ntiles_of(m0);
-  const size_t tbytes = (size_t)grid * kWavesPerBlock * (1u << kWinMul) * rad_ll(TPI) * FPHE_WAVE * 4;
-  const size_t o_need = tbytes, o_eb = o_need + nt * FPHE_WAVE, o_E = o_eb + nt * FPHE_WAVE * 4;
-  const size_t o_inv = o_E + nt * L1 * FPHE_WAVE * 4, o_x0 = o_inv + nt * L * FPHE_WAVE * 4;
-  const size_t x0b = nt * L1 * FPHE_WAVE * 4, binvb = m0 >= binv_min() ? binv_scratch_bytes<L>(m0) : 0;
-  if (ensure_scratch(c, o_x0 + (binvb > x0b ? binvb : x0b), s) != FPHE_OK) return FPHE_ERR_HIP;
+  const size_t nt = ntiles_of(sp.m0);
+  const size_t tbytes = G::table_bytes(sp.grid, 1 << kWinMul);
+  const size_t at_need = tbytes, at_eb = at_need + nt * FPHE_WAVE, at_E = at_eb + nt * FPHE_WAVE * 4;
+  const size_t at_inv = at_E + nt * L1 * FPHE_WAVE * 4, at_x0 = at_inv + nt * L * FPHE_WAVE * 4;
+  const size_t x0b = nt * L1 * FPHE_WAVE * 4, binvb = sp.m0 >= binv_min() ? binv_scratch_bytes<L>(sp.m0) : 0;
+  if (ensure_scratch(c, at_x0 + (binvb > x0b ? binvb : x0b), s) != FPHE_OK) return FPHE_ERR_HIP;
   char* base = reinterpret_cast<char*>(c->scratch);
-  u8* need = reinterpret_cast<u8*>(base + o_need);
-  int32_t* eb = reinterpret_cast<int32_t*>(base + o_eb);
-  u32* Ex = reinterpret_cast<u32*>(base + o_E);
-  u32* Cinv = reinterpret_cast<u32*>(base + o_inv);
-  u32* X0 = reinterpret_cast<u32*>(base + o_x0);
-  for (size_t e0 = 0; e0 < count; e0 += span) {
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
+  u8* need = reinterpret_cast<u8*>(base + at_need);
+  int32_t* eb = reinterpret_cast<int32_t*>(base + at_eb);
+  u32* Ex = reinterpret_cast<u32*>(base + at_E);
+  u32* Cinv = reinterpret_cast<u32*>(base + at_inv);
+  u32* X0 = reinterpret_cast<u32*>(base + at_x0);
+  return for_spans(count, sp.span, [&](size_t e0, size_t m, size_t t0) {
     const uint32_t* Cs = Ca + t0 * L * FPHE_WAVE;
     const uint32_t* Ps = pstride ? P + t0 * lp * FPHE_WAVE : P;
     const uint8_t* ns = pstride ? pneg + e0 : pneg;
     const int32_t* xs = pstride ? pexp + e0 : pexp;
-    const unsigned pgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 8);
+    const unsigned pgrid = lane_grid(c, m, 8);
     if (c->ou) {  // plain c^pt mod n: no sign branches, nothing to invert
       hipLaunchKernelGGL(k_ou_mul_prep<L>, dim3(pgrid), dim3(256), 0, s, Ps, lp, pstride, m, need, Ex, eb);
     } else {
@@ -1689,253 +1637,72 @@ fphe_status launch_mul27(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, con
       else
         launch_inv27<L>(c, Cs, m, need, Cinv, err, X0, s);
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, Cs, Cinv, need, ea + e0, Ex, eb, xs, pstride, m,
-                       Co + t0 * L * FPHE_WAVE, so + e0, eo + e0, c->scratch, (u32)NL);
-    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
+    hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kBlock), G::lds(), s, c->K, Cs, Cinv, need, ea + e0, Ex, eb, xs, pstride,
+                       m, Co + t0 * L * FPHE_WAVE, so + e0, eo + e0, c->scratch, (u32)G::NL);
+    return hip_ok(hipGetLastError());
+  });
 }
 
-
-
-// ---- wire format: bincode(serde(rug::Integer)) records (fate_utils pickles) ------------
-// A reference Ciphertext / Plaintext serializes (bincode 1.3 fixint, little endian) as
-//   i32 radix | u64 len | len ASCII chars ("-"? + digits, no leading zeros) | i32 exp
-// (BInt is a newtype over rug::Integer, math/src/rug/mod.rs:11; rug's serde writes an
-// Integer as the struct {radix, value}; pickles are bincode::serialize, paillier.rs:219-226).
-// rug picks the radix per value: decimal when the magnitude has at most 32 significant bits,
-// lowercase hex otherwise (rug 1.20 integer/serde.rs; unpinned).  mag is
-// element-major LSF uint32 [count][L] (fphe_export_signed).
-__device__ __forceinline__ u32 dec_digits(u32 w) {
-  u32 d = 1;
-  for (u64 p = 10; p <= w; p *= 10) ++d;
-  return d;
-}
-
-// digits and radix of one magnitude
-__device__ __forceinline__ u32 wire_digits(const u32* __restrict__ m, u32 L, u32& radix) {
-  int k = (int)L - 1;
-  while (k > 0 && m[k] == 0) --k;
-  const u32 w = m[k];
-  if (k == 0) {
-    radix = 10;
-    return dec_digits(w);
-  }
-  radix = 16;
-  const u32 nib = (32u - (u32)__builtin_clz(w) + 3u) / 4u;
-  return (u32)k * 8u + nib;
-}
-
-__global__ __launch_bounds__(256) void k_wire_lengths(const u32* __restrict__ mag, const u8* __restrict__ neg, u32 L,
-                                                      size_t count, int64_t* __restrict__ rec_len,
-                                                      u8* __restrict__ radix) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= count) return;
-  u32 rdx;
-  const u32 nd = wire_digits(mag + e * L, L, rdx);
-  rec_len[e] = 4 + 8 + 4 + (int64_t)(neg[e] ? 1 : 0) + (int64_t)nd;
-  radix[e] = (u8)rdx;
-}
-
-// one thread per (element, 32-bit word): for a hex record the word's 8 nibbles are digit
-// positions 8k .. 8k+7 from the least significant end; word 0's thread also writes the
-// header, the sign and the exponent, and all digits of a decimal (<= 32-bit) record.
-__global__ __launch_bounds__(256) void k_wire_encode(const u32* __restrict__ mag, const u8* __restrict__ neg,
-                                                     const int32_t* __restrict__ exp, u32 L, size_t count,
-                                                     const int64_t* __restrict__ rec_off,
-                                                     const int64_t* __restrict__ rec_len, const u8* __restrict__ radix,
-                                                     u8* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= count * L) return;
-  const size_t e = t / L;
-  const u32 k = (u32)(t % L);
-  const u32* m = mag + e * L;
-  const u32 sg = neg[e] ? 1u : 0u;
-  const u32 digits = (u32)(rec_len[e] - 16 - sg);
-  const u32 rdx = radix[e];
-  if (rdx == 10 && k != 0) return;
-  if (rdx != 10 && 8u * k >= digits) return;
-  u8* r = out + rec_off[e];
-  u8* d = r + 12 + sg;
-  if (k == 0) {
-    const uint64_t len = digits + sg;
-    r[0] = (u8)rdx; r[1] = 0; r[2] = 0; r[3] = 0;
-    for (int b = 0; b < 8; ++b) r[4 + b] = (u8)(len >> (8 * b));
-    if (sg) r[12] = '-';
-    const u32 x = (u32)exp[e];
-    u8* ex = r + 12 + sg + digits;
-    for (int b = 0; b < 4; ++b) ex[b] = (u8)(x >> (8 * b));
-    if (rdx == 10) {
-      u32 w = m[0];
-      for (u32 j = 0; j < digits; ++j) {
-        d[digits - 1 - j] = (u8)('0' + w % 10u);
-        w /= 10u;
-      }
-      return;
+// ---- Okamoto-Uchiyama (ou_dev.h): L <= 128, no TPI-8 OU kernel exists ---------------------
+template <int L>
+fphe_status launch_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
+                              const uint32_t key[8], uint64_t nonce, uint32_t* C, hipStream_t s) {
+  using G = Engine<L>;
+  auto kern = OU<G::TPI>::template encrypt<L, kOuWin>();
+  const Spans sp = prep_spans<G>(c, kern, G::lds(), count, "ou_encrypt27");
+  const ChaChaKey ck = chacha_key(r ? nullptr : key);
+  if (!r && ensure_scratch(c, tile_bytes(sp.m0, L), s) != FPHE_OK) return FPHE_ERR_HIP;
+  return for_spans(count, sp.span, [&](size_t e0, size_t m, size_t t0) {
+    const u32* rbuf = r ? r + t0 * L * FPHE_WAVE : nullptr;
+    if (!r) {  // draw_r over the L words of n (K.nm1, K.nbits of an OU context)
+      hipLaunchKernelGGL(k_draw_r<L>, dim3(lane_grid(c, m, 4)), dim3(256), 0, s, c->K, m, ck, nonce, e0, c->scratch);
+      rbuf = c->scratch;
     }
-  }
-  const u32 w = m[k];
-  for (u32 i = 0; i < 8; ++i) {
-    const u32 j = 8u * k + i;
-    if (j >= digits) break;
-    const u32 nib = (w >> (4 * i)) & 15u;
-    d[digits - 1 - j] = (u8)(nib < 10 ? '0' + nib : 'a' + nib - 10);
-  }
+    hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kBlock), G::lds(), s, c->K, c->ou_tab, c->ou_hwin,
+                       P + t0 * lp * FPHE_WAVE, lp, rbuf, m, C + t0 * L * FPHE_WAVE, (u32)G::NL);
+    return hip_ok(hipGetLastError());
+  });
 }
 
-// digit strings back to magnitude words (radix 16: one thread per word; radix 10 with at
-// most 19 digits: word 0's thread writes words 0 and 1; other radixes are parsed on the
-// host).  err bit 0: a character that is not a digit of the radix, bit 1: a value wider
-// than L words.
-__global__ __launch_bounds__(256) void k_wire_decode(const u8* __restrict__ buf, const int64_t* __restrict__ dig_off,
-                                                     const int32_t* __restrict__ dig_len, const int32_t* __restrict__ radix,
-                                                     u32 L, size_t count, u32* __restrict__ mag,
-                                                     int32_t* __restrict__ err) {
-  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= count * L) return;
-  const size_t e = t / L;
-  const u32 k = (u32)(t % L);
-  const int64_t off = dig_off[e];
-  const u32 len = (u32)dig_len[e];
-  u32 bad = 0;
-  if (radix[e] == 10) {
-    if (k == 0) {
-      u64 v = 0;
-      for (u32 i = 0; i < len; ++i) {
-        const u32 ch = buf[off + i];
-        if (ch < '0' || ch > '9') { bad |= 1u; break; }
-        v = v * 10u + (ch - '0');
-      }
-      mag[e * L] = (u32)v;
-      if (L > 1) mag[e * L + 1] = (u32)(v >> 32);
-      else if (v >> 32) bad |= 2u;
-    } else if (k > 1) {
-      mag[e * L + k] = 0;
-    }
-    if (bad) atomicOr(err, (int32_t)bad);
-    return;
-  }
-  u32 w = 0;
-  for (u32 i = 0; i < 8; ++i) {
-    const u32 j = 8u * k + i;
-    if (j >= len) break;
-    const u32 ch = buf[off + len - 1 - j];
-    u32 v;
-    if (ch >= '0' && ch <= '9') v = ch - '0';
-    else if (ch >= 'a' && ch <= 'f') v = ch - 'a' + 10;
-    else if (ch >= 'A' && ch <= 'F') v = ch - 'A' + 10;
-    else { v = 0; bad |= 1u; }
-    w |= v << (4 * i);
-  }
-  mag[e * L + k] = w;
-  if (k == L - 1) {  // digits past the top word must be zeros
-    for (u32 j = 8u * L; j < len; ++j) {
-      const u32 ch = buf[off + len - 1 - j];
-      if (ch != '0') { bad |= 2u; break; }
-    }
-  }
-  if (bad) atomicOr(err, (int32_t)bad);
+template <int L>
+fphe_status launch_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, hipStream_t s) {
+  using G = Engine<L>;
+  constexpr int LQ = L / 2;
+  auto kern = OU<G::TPI>::template decrypt<L, kWinSlide>();
+  const Spans sp = prep_spans<G>(c, kern, G::lds(), count, "ou_decrypt27");
+  const size_t tbytes = G::table_bytes(sp.grid, kTabEntries<kWinSlide>);
+  if (ensure_scratch(c, tbytes + tile_bytes(sp.m0, L), s) != FPHE_OK) return FPHE_ERR_HIP;
+  u32* Y = c->scratch + tbytes / 4;
+  auto ktail = k_ou_decrypt_tail<L>;
+  const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;
+  set_lds(ktail, lds2);
+  return for_spans(count, sp.span, [&](size_t, size_t m, size_t t0) {
+    hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kBlock), G::lds(), s, c->K, C + t0 * L * FPHE_WAVE, m, Y, c->scratch,
+                       (u32)G::NL);
+    hipLaunchKernelGGL(ktail, dim3(grid_for(c, m, bpc_for_slot(LQ))), dim3(kBlock), lds2, s, c->K, (const u32*)Y,
+                       ntiles_of(m), P + t0 * LQ * FPHE_WAVE);
+    return hip_ok(hipGetLastError());
+  });
 }
 
-// ---- element permutation of tile-major vectors (gather / scatter) ---------------------
-// One thread per 32-bit word of the contiguous side, so that side is read or written fully
-// coalesced; the indexed side follows idx (stable sorts and slices keep it mostly local).
-// Indexes outside [0, nspace) are skipped; the host checks them before the call.
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void k_permute(const u32* __restrict__ Cin, const u8* __restrict__ sin,
-                                                 const int32_t* __restrict__ ein, u32 L,
-                                                 const int64_t* __restrict__ idx, size_t count, size_t nspace,
-                                                 u32* __restrict__ Cout, u8* __restrict__ sout,
-                                                 int32_t* __restrict__ eout) {
-  const size_t per_tile = (size_t)L * FPHE_WAVE;
-  const size_t total = ((count + FPHE_WAVE - 1) / FPHE_WAVE) * per_tile;
-  for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (size_t)gridDim.x * blockDim.x) {
-    const size_t tile = o / per_tile, rem = o - tile * per_tile;
-    const u32 w = (u32)(rem >> 6), col = (u32)(rem & 63);
-    const size_t i = tile * FPHE_WAVE + col;  // position on the contiguous side
-    if (i >= count) continue;
-    const int64_t j = idx[i];
-    if (j < 0 || (size_t)j >= nspace) continue;
-    const size_t oj = ((size_t)j >> 6) * per_tile + (size_t)w * FPHE_WAVE + ((size_t)j & 63);
-    if (SCATTER) {
-      if (Cin) Cout[oj] = Cin[o];
-      if (w == 0) {
-        if (sin) sout[j] = sin[i];
-        if (ein) eout[j] = ein[i];
-      }
-    } else {
-      if (Cin) Cout[o] = Cin[oj];
-      if (w == 0) {
-        if (sin) sout[i] = sin[j];
-        if (ein) eout[i] = ein[j];
-      }
-    }
-  }
-}
-
-// ---- (C, sign) <-> the reference's signed integers ------------------------------------
-// The reference's ciphertext is the signed rug::Integer C - sign n^2 (canonical C, SURVEY.md
-// §0 fact 1).  Export writes its magnitude as element-major LSF words and a negative flag;
-// import is the inverse.  One thread per element; the tile-major side is coalesced.
-__global__ __launch_bounds__(256) void k_export_signed(const u32* __restrict__ N2, u32 L, const u32* __restrict__ C,
-                                                       const u8* __restrict__ sign, size_t count,
-                                                       u32* __restrict__ mag, u8* __restrict__ neg) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= count) return;
-  const u32* c = C + (e >> 6) * (size_t)L * FPHE_WAVE + (e & 63);
-  u32* m = mag + e * L;
-  u32 nz = 0;
-  for (u32 w = 0; w < L; ++w) nz |= c[(size_t)w * FPHE_WAVE];
-  const bool ng = sign[e] != 0 && nz != 0;
-  u32 borrow = 0;
-  for (u32 w = 0; w < L; ++w) {
-    const u32 cw = c[(size_t)w * FPHE_WAVE];
-    if (ng) {  // n^2 - C
-      const u64 d = (u64)N2[w] - cw - borrow;
-      m[w] = (u32)d;
-      borrow = (u32)(d >> 63);
-    } else {
-      m[w] = cw;
-    }
-  }
-  neg[e] = ng ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void k_import_signed(const u32* __restrict__ N2, u32 L, const u32* __restrict__ mag,
-                                                       const u8* __restrict__ neg, size_t count, u32* __restrict__ C,
-                                                       u8* __restrict__ sign) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= count) return;
-  u32* c = C + (e >> 6) * (size_t)L * FPHE_WAVE + (e & 63);
-  const u32* m = mag + e * L;
-  u32 nz = 0;
-  for (u32 w = 0; w < L; ++w) nz |= m[w];
-  const bool ng = neg[e] != 0 && nz != 0;
-  u32 borrow = 0;
-  for (u32 w = 0; w < L; ++w) {
-    if (ng) {  // canonical n^2 - |c|
-      const u64 d = (u64)N2[w] - m[w] - borrow;
-      c[(size_t)w * FPHE_WAVE] = (u32)d;
-      borrow = (u32)(d >> 63);
-    } else {
-      c[(size_t)w * FPHE_WAVE] = m[w];
-    }
-  }
-  sign[e] = ng ? 1 : 0;
-}
-}  // namespace
-
-namespace {
 // The device half of context creation, shared by fphe_ctx_create and fphe_ou_ctx_create: the
-// path-option defaults, the CU count, the pool threshold and the key blob's upload.  Call with
-// the device current; on failure nothing is left allocated (the caller deletes c).
-fphe_status ctx_device_init(fphe_ctx* c, int device, const std::vector<u32>& blob) {
+// scalars and KeyArgs of the built key, the path-option defaults, the CU count, the pool
+// threshold and the key blob's upload.  Returns the new context, or null on a HIP failure
+// (nothing is left allocated).
+fphe_ctx* ctx_from_blob(int device, uint32_t key_bits, bool ou, const KeyBlob& B) {
+  auto* c = new fphe_ctx();
+  c->device = device; c->key_bits = key_bits; c->L1 = B.L1; c->L2 = B.L2; c->LQ = B.LQ; c->has_sk = B.has_sk;
+  c->kh_direct = B.has_sk && B.kh_direct;
+  c->ou = ou;
+  c->ou_hwin = B.ou_hwin;
+  // (the wide_* path options are stored and read back but select nothing on an OU context)
   c->wide_decrypt_max = env_i64("FPHE_WIDE_DECRYPT_MAX", 4096);
   c->wide_encrypt_max = env_i64("FPHE_WIDE_ENCRYPT_MAX", 2048);
   c->wide_kh_encrypt_max = env_i64("FPHE_WIDE_KH_ENCRYPT_MAX", 4096);
   c->kh_direct_z = env_i64("FPHE_KH_DIRECT_Z", 1) != 0;
+  DevGuard g(device);
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FPHE_ERR_HIP;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete c; return nullptr; }
   c->cus = prop.multiProcessorCount;
   {
     // fphe_fold_segments takes its scratch from the device's default stream-ordered pool:
@@ -1948,13 +1715,16 @@ fphe_status ctx_device_init(fphe_ctx* c, int device, const std::vector<u32>& blo
       (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
     }
   }
-  if (hipMalloc(&c->blob, blob.size() * 4) != hipSuccess) { c->blob = nullptr; return FPHE_ERR_HIP; }
-  if (hipMemcpy(c->blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+  const size_t bytes = B.words.size() * 4;
+  if (hipMalloc(&c->blob, bytes) != hipSuccess) { delete c; return nullptr; }
+  if (hipMemcpy(c->blob, B.words.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(c->blob);
-    c->blob = nullptr;
-    return FPHE_ERR_HIP;
+    delete c;
+    return nullptr;
   }
-  return FPHE_OK;
+  c->K = B.resolve(c->blob);
+  if (ou) c->ou_tab = c->blob + B.ou_tab;
+  return c;
 }
 }  // namespace
 
@@ -1963,178 +1733,32 @@ extern "C" {
 fphe_status fphe_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, const uint32_t* p_w,
                             const uint32_t* q_w, fphe_ctx** out) {
   if (!out || !n_w) return FPHE_ERR_ARG;
-  // any even size up to 4096 bits (paillier/src/lib.rs:72-87 accepts any even size): the
-  // kernels run the 1024-, 2048- or 4096-bit geometry with n zero-padded to it (R >= 4N
-  // holds, so the lazy Montgomery bounds are unchanged).  Above 2048 bits n^2 spans 8 lanes
-  // per element (TPI 8, 296 limbs of 28 bits) and n, p^2, q^2 the TPI-4 geometry.
   if (key_bits < 256 || key_bits > 4096 || key_bits % 2) return FPHE_ERR_ARG;
   if ((p_w == nullptr) != (q_w == nullptr)) return FPHE_ERR_ARG;
-  const int L1 = key_bits <= 1024 ? 32 : (key_bits <= 2048 ? 64 : 128), L2 = 2 * L1, LQ = L1 / 2;
-  try {
-    Limbs n = from_words(n_w, L1);
-    if (n.empty() || !(n[0] & 1)) return FPHE_ERR_KEY;
-    if (hbn::bitlen(n) != key_bits) return FPHE_ERR_KEY;  // paillier/src/lib.rs:82 keeps bits(n)==k
-    Limbs N2 = hbn::mul(n, n);
-    std::vector<std::pair<const char*, Limbs>> arrays;
-    std::vector<u32> blob;
-    auto put = [&](const Limbs& v, size_t len) -> size_t {
-      const size_t off = blob.size();
-      Limbs p = hbn::padded(v, len);
-      blob.insert(blob.end(), p.begin(), p.end());
-      while (blob.size() % 4) blob.push_back(0);  // 16-byte aligned sections
-      return off;
-    };
-    const size_t o_N2 = put(N2, L2);
-    const size_t o_N2R2 = put(hbn::pow2_mod((size_t)64 * L2, N2), L2);
-    const size_t o_N2R1 = put(hbn::pow2_mod((size_t)32 * L2, N2), L2);
-    const size_t o_n = put(n, L1 + 1);
-    const size_t o_nm1 = put(hbn::sub(n, Limbs{1}), L1);
-    Limbs max_int = n;  // floor(n/2)
-    for (size_t i = 0; i < max_int.size(); ++i)
-      max_int[i] = (max_int[i] >> 1) | (i + 1 < max_int.size() ? max_int[i + 1] << 31 : 0);
-    max_int = hbn::norm(max_int);
-    const size_t o_max = put(max_int, L1);
-    const size_t o_nmm = put(hbn::sub(n, max_int), L1);
-    // engine limbs: n^2 at TPI2 = L2/32 lanes, n / p^2 / q^2 at TPIh = L2/64, each in the
-    // radix of its engine (mont27_dev.h: 27 bits at TPI 4, 28 below); R = 2^(LB NL)
-    const int TPI2 = L2 / 32, TPIh = L2 / 64;
-    const int LB2 = rad_lb(TPI2), LBh = rad_lb(TPIh);
-    const int NL2 = rad_ll(TPI2) * TPI2, NLh = rad_ll(TPIh) * TPIh;
-    auto to27 = [](const Limbs& v, int nl, int lb) { return to_radix(v, nl, lb); };
-    const size_t o_N2_27 = put(to27(N2, NL2, LB2), NL2);
-    const size_t o_N2R1_27 = put(to27(hbn::pow2_mod((size_t)LB2 * NL2, N2), NL2, LB2), NL2);
-    const size_t o_N2R2_27 = put(to27(hbn::pow2_mod((size_t)2 * LB2 * NL2, N2), NL2, LB2), NL2);
-    const size_t o_N2R3_27 = put(to27(hbn::pow2_mod((size_t)3 * LB2 * NL2, N2), NL2, LB2), NL2);
-    const size_t o_N2M1 = put(hbn::pow2_mod((size_t)LB2 * NL2, N2), L2);
-    const size_t o_Nn_27 = put(to27(n, NLh, LBh), NLh);
-    const size_t o_NnR1_27 = put(to27(hbn::pow2_mod((size_t)LBh * NLh, n), NLh, LBh), NLh);
-    const size_t o_NnR2_27 = put(to27(hbn::pow2_mod((size_t)2 * LBh * NLh, n), NLh, LBh), NLh);
-    size_t o_P2_27 = 0, o_P2R1_27 = 0, o_P2R2_27 = 0, o_Q2_27 = 0, o_Q2R1_27 = 0, o_Q2R2_27 = 0;
-    size_t o_P2 = 0, o_P2R3 = 0, o_pm1 = 0, o_p = 0, o_pinv2 = 0, o_hpR = 0;
-    size_t o_Q2 = 0, o_Q2R3 = 0, o_qm1 = 0, o_q = 0, o_qinv2 = 0, o_hqR = 0, o_pinvqR = 0;
-    u32 p2n0 = 0, pn0 = 0, q2n0 = 0, qn0 = 0;
-    int pm1b = 0, qm1b = 0, epb = 0, eqb = 0;
-    size_t o_ep = 0, o_eq = 0, o_KpR = 0, o_KqR = 0, o_P2RX_27 = 0, o_Q2RX_27 = 0;
-    size_t o_Ps = 0, o_PsR2 = 0, o_PsR3 = 0, o_Qs = 0, o_QsR2 = 0, o_QsR3 = 0, o_e1p = 0, o_e1q = 0;
-    u32 ps_np = 0, qs_np = 0;
-    int e1pb = 0, e1qb = 0, pb = 0, qb = 0;
-    bool kh_direct = false;
-    const bool has_sk = p_w != nullptr;
-    if (has_sk) {
-      Limbs p = from_words(p_w, LQ), q = from_words(q_w, LQ);
-      if (hbn::cmp(p, q) == 0) return FPHE_ERR_KEY;
-      if (hbn::cmp(p, q) > 0) std::swap(p, q);  // SK::new keeps p < q (paillier/src/lib.rs:127)
-      if (hbn::cmp(hbn::mul(p, q), n) != 0) return FPHE_ERR_KEY;
-      if (!(p[0] & 1) || !(q[0] & 1)) return FPHE_ERR_KEY;
-      Limbs P2 = hbn::mul(p, p), Q2 = hbn::mul(q, q);
-      Limbs pm1 = hbn::sub(p, Limbs{1}), qm1 = hbn::sub(q, Limbs{1});
-      // h_p = ((g^(p-1) mod p^2 - 1)/p)^{-1} mod p with g = n+1 (paillier/src/lib.rs:131-137);
-      // (1+n)^(p-1) = 1 + (p-1) n (mod p^2), so the L-value is (p-1) q mod p.
-      auto hval = [&](const Limbs& s, const Limbs& t) {
-        Limbs Lv = hbn::mod(hbn::mul(hbn::sub(s, Limbs{1}), t), s);
-        return hbn::inv_mod(Lv, s);
-      };
-      Limbs hp = hval(p, q), hq = hval(q, p);
-      Limbs pinvq = hbn::inv_mod(p, q);
-      o_P2 = put(P2, L1);
-      o_P2R3 = put(hbn::pow2_mod((size_t)96 * L1, P2), L1);
-      o_pm1 = put(pm1, LQ + 1);
-      o_p = put(p, LQ);
-      o_pinv2 = put(hbn::inv_pow2(p, LQ), LQ);
-      o_hpR = put(hbn::mod(hbn::mul(hp, hbn::pow2_mod((size_t)32 * LQ, p)), p), LQ);
-      o_Q2 = put(Q2, L1);
-      o_Q2R3 = put(hbn::pow2_mod((size_t)96 * L1, Q2), L1);
-      o_qm1 = put(qm1, LQ + 1);
-      o_q = put(q, LQ);
-      o_qinv2 = put(hbn::inv_pow2(q, LQ), LQ);
-      o_hqR = put(hbn::mod(hbn::mul(hq, hbn::pow2_mod((size_t)32 * LQ, q)), q), LQ);
-      o_pinvqR = put(hbn::mod(hbn::mul(pinvq, hbn::pow2_mod((size_t)32 * LQ, q)), q), LQ);
-      o_P2_27 = put(to27(P2, NLh, LBh), NLh);
-      o_P2R1_27 = put(to27(hbn::pow2_mod((size_t)LBh * NLh, P2), NLh, LBh), NLh);
-      o_P2R2_27 = put(to27(hbn::pow2_mod((size_t)2 * LBh * NLh, P2), NLh, LBh), NLh);
-      o_Q2_27 = put(to27(Q2, NLh, LBh), NLh);
-      o_Q2R1_27 = put(to27(hbn::pow2_mod((size_t)LBh * NLh, Q2), NLh, LBh), NLh);
-      o_Q2R2_27 = put(to27(hbn::pow2_mod((size_t)2 * LBh * NLh, Q2), NLh, LBh), NLh);
-      // R_s^2 R^-1 mod s^2 (R of n^2, R_s of s^2): mont_s(M(c) mod s^2, .) = c R_s
-      auto rx = [&](const Limbs& S2) {
-        const Limbs Rn = hbn::pow2_mod((size_t)LB2 * NL2, S2);
-        return hbn::mod(hbn::mul(hbn::pow2_mod((size_t)2 * LBh * NLh, S2), hbn::inv_mod(Rn, S2)), S2);
-      };
-      o_P2RX_27 = put(to27(rx(P2), NLh, LBh), NLh);
-      o_Q2RX_27 = put(to27(rx(Q2), NLh, LBh), NLh);
-      p2n0 = hbn::neg_inv32(P2[0]); pn0 = hbn::neg_inv32(p[0]);
-      q2n0 = hbn::neg_inv32(Q2[0]); qn0 = hbn::neg_inv32(q[0]);
-      pm1b = (int)hbn::bitlen(pm1); qm1b = (int)hbn::bitlen(qm1);
-      // CRT encryption constants
-      Limbs ep = hbn::mod(n, hbn::mul(p, pm1)), eq = hbn::mod(n, hbn::mul(q, qm1));
-      o_ep = put(ep, L1);
-      o_eq = put(eq, L1);
-      epb = (int)hbn::bitlen(ep); eqb = (int)hbn::bitlen(eq);
-      {  // the split key-holder modexp's constants (KeyArgs)
-        const int TPIs = L2 >= 128 ? L2 / 128 : 1, LBs = rad_lb(TPIs), NLs = rad_ll(TPIs) * TPIs;
-        o_Ps = put(to27(p, NLs, LBs), NLs);
-        o_PsR2 = put(to27(hbn::pow2_mod((size_t)2 * LBs * NLs, p), NLs, LBs), NLs);
-        o_PsR3 = put(to27(hbn::pow2_mod((size_t)3 * LBs * NLs, p), NLs, LBs), NLs);
-        o_Qs = put(to27(q, NLs, LBs), NLs);
-        o_QsR2 = put(to27(hbn::pow2_mod((size_t)2 * LBs * NLs, q), NLs, LBs), NLs);
-        o_QsR3 = put(to27(hbn::pow2_mod((size_t)3 * LBs * NLs, q), NLs, LBs), NLs);
-        ps_np = hbn::neg_inv32(p[0]) & ((1u << LBs) - 1u);
-        qs_np = hbn::neg_inv32(q[0]) & ((1u << LBs) - 1u);
-        const Limbs e1p = hbn::mod(q, pm1), e1q = hbn::mod(p, qm1);
-        o_e1p = put(e1p, LQ);
-        o_e1q = put(e1q, LQ);
-        e1pb = (int)hbn::bitlen(e1p); e1qb = (int)hbn::bitlen(e1q);
-        pb = (int)hbn::bitlen(p); qb = (int)hbn::bitlen(q);
-        // p, q prime: gcd(q, p - 1) = 1 iff q does not divide p - 1 (and likewise)
-        kh_direct = !hbn::is_zero(hbn::mod(pm1, q)) && !hbn::is_zero(hbn::mod(qm1, p));
-      }
-      const Limbs R27 = hbn::pow2_mod((size_t)LB2 * NL2, N2);
-      const Limbs Kp = hbn::mul(Q2, hbn::inv_mod(hbn::mod(Q2, P2), P2));  // < n^2
-      const Limbs Kq = hbn::mul(P2, hbn::inv_mod(hbn::mod(P2, Q2), Q2));
-      o_KpR = put(to27(hbn::mod(hbn::mul(Kp, R27), N2), NL2, LB2), NL2);
-      o_KqR = put(to27(hbn::mod(hbn::mul(Kq, R27), N2), NL2, LB2), NL2);
-    }
-    auto* c = new fphe_ctx();
-    c->device = device; c->key_bits = key_bits; c->L1 = L1; c->L2 = L2; c->LQ = LQ; c->has_sk = has_sk;
-    c->kh_direct = has_sk && kh_direct;
-    DevGuard g(device);
-    if (ctx_device_init(c, device, blob) != FPHE_OK) { delete c; return FPHE_ERR_HIP; }
-    u32* b = c->blob;
-    KeyArgs& K = c->K;
-    K.N2 = b + o_N2; K.N2_R2 = b + o_N2R2; K.N2_R1 = b + o_N2R1; K.n = b + o_n; K.nm1 = b + o_nm1;
-    K.max_int = b + o_max; K.n_mm = b + o_nmm;
-    K.n2_n0inv = hbn::neg_inv32(N2[0]);
-    K.nbits = (int)key_bits;
-    K.N2_27 = b + o_N2_27; K.N2R1_27 = b + o_N2R1_27; K.N2R2_27 = b + o_N2R2_27;
-    K.n2_np27 = K.n2_n0inv & ((1u << LB2) - 1u);
-    K.N2R3_27 = b + o_N2R3_27;
-    K.N2M1 = b + o_N2M1;
-    K.Nn_27 = b + o_Nn_27; K.NnR1_27 = b + o_NnR1_27; K.NnR2_27 = b + o_NnR2_27;
-    K.nn_np27 = hbn::neg_inv32(n[0]) & ((1u << LBh) - 1u);
-    K.nn_inv27 = (0u - hbn::neg_inv32(n[0])) & ((1u << LBh) - 1u);
-    if (has_sk) {
-      K.P2 = b + o_P2; K.P2_R3 = b + o_P2R3; K.pm1 = b + o_pm1; K.p = b + o_p; K.pinv2 = b + o_pinv2; K.hpR = b + o_hpR;
-      K.Q2 = b + o_Q2; K.Q2_R3 = b + o_Q2R3; K.qm1 = b + o_qm1; K.q = b + o_q; K.qinv2 = b + o_qinv2; K.hqR = b + o_hqR;
-      K.pinvqR = b + o_pinvqR;
-      K.p2_n0inv = p2n0; K.p_n0inv = pn0; K.q2_n0inv = q2n0; K.q_n0inv = qn0;
-      K.pm1_bits = pm1b; K.qm1_bits = qm1b;
-      K.P2_27 = b + o_P2_27; K.P2R1_27 = b + o_P2R1_27; K.P2R2_27 = b + o_P2R2_27;
-      K.Q2_27 = b + o_Q2_27; K.Q2R1_27 = b + o_Q2R1_27; K.Q2R2_27 = b + o_Q2R2_27;
-      K.p2_np27 = p2n0 & ((1u << LBh) - 1u); K.q2_np27 = q2n0 & ((1u << LBh) - 1u);
-      K.ep = b + o_ep; K.eq = b + o_eq; K.ep_bits = epb; K.eq_bits = eqb;
-      K.KpR_27 = b + o_KpR; K.KqR_27 = b + o_KqR;
-      K.P2RX_27 = b + o_P2RX_27; K.Q2RX_27 = b + o_Q2RX_27;
-      K.Ps_27 = b + o_Ps; K.PsR2_27 = b + o_PsR2; K.PsR3_27 = b + o_PsR3;
-      K.Qs_27 = b + o_Qs; K.QsR2_27 = b + o_QsR2; K.QsR3_27 = b + o_QsR3;
-      K.ps_np27 = ps_np; K.qs_np27 = qs_np;
-      K.e1p = b + o_e1p; K.e1q = b + o_e1q;
-      K.e1p_bits = e1pb; K.e1q_bits = e1qb; K.p_bits = pb; K.q_bits = qb;
-    }
-    *out = c;
-    return FPHE_OK;
-  } catch (...) {
-    return FPHE_ERR_KEY;
-  }
+  KeyBlob B;
+  const fphe_status st = build_paillier_blob(key_bits, n_w, p_w, q_w, B);
+  if (st != FPHE_OK) return st;
+  fphe_ctx* c = ctx_from_blob(device, key_bits, false, B);
+  if (!c) return FPHE_ERR_HIP;
+  *out = c;
+  return FPHE_OK;
+}
+
+// Okamoto-Uchiyama (rust/fate_utils/crates/ou/src/lib.rs:69-138).  Every entry point but
+// fphe_ou_encrypt / fphe_ou_decrypt reaches an OU context through the N2* slots of KeyArgs,
+// which hold n = p^2 q.
+fphe_status fphe_ou_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, const uint32_t* g_w,
+                               const uint32_t* h_w, const uint32_t* p_w, const uint32_t* q_w, fphe_ctx** out) {
+  if (!out || !n_w || !g_w || !h_w) return FPHE_ERR_ARG;
+  if (key_bits < 1024 || key_bits > 4096 || key_bits % 2) return FPHE_ERR_ARG;
+  if ((p_w == nullptr) != (q_w == nullptr)) return FPHE_ERR_ARG;
+  KeyBlob B;
+  const fphe_status st = build_ou_blob(key_bits, n_w, g_w, h_w, p_w, q_w, B);
+  if (st != FPHE_OK) return st;
+  fphe_ctx* c = ctx_from_blob(device, key_bits, true, B);
+  if (!c) return FPHE_ERR_HIP;
+  *out = c;
+  return FPHE_OK;
 }
 
 fphe_status fphe_ctx_destroy(fphe_ctx* c) {
@@ -2188,7 +1812,7 @@ fphe_status fphe_encode_f32(const fphe_ctx* c, const float* x, size_t count, uin
   if (count == 0) return FPHE_OK;
   if (!x || !P || !neg || !exp) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
+  const unsigned grid = lane_grid(c, count, 8);
   hipLaunchKernelGGL(k_encode_f32, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, count, P, neg, exp, err);
   return hip_ok(hipGetLastError());
 }
@@ -2199,7 +1823,7 @@ fphe_status fphe_encode_f64(const fphe_ctx* c, const double* x, size_t count, ui
   if (count == 0) return FPHE_OK;
   if (!x || !P || !neg || !exp) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
+  const unsigned grid = lane_grid(c, count, 8);
   hipLaunchKernelGGL(k_encode_f64, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, count, P, neg, exp, err);
   return hip_ok(hipGetLastError());
 }
@@ -2211,13 +1835,11 @@ fphe_status fphe_decode_f32(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_decode_f32<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_decode_f32<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else
-    hipLaunchKernelGGL(k_decode_f32<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
+  const unsigned grid = lane_grid(c, count, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_decode_f32<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count,
+                       out, err);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2228,13 +1850,11 @@ fphe_status fphe_decode_f64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_decode_f64<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_decode_f64<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else
-    hipLaunchKernelGGL(k_decode_f64<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
+  const unsigned grid = lane_grid(c, count, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_decode_f64<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count,
+                       out, err);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2246,13 +1866,11 @@ fphe_status fphe_encode_i64(const fphe_ctx* c, const int64_t* x, size_t count, u
   if (count == 0) return FPHE_OK;
   if (!x || !P || !neg || !exp) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_encode_i64<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, x, count, P, neg, exp);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_encode_i64<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, x, count, P, neg, exp);
-  else
-    hipLaunchKernelGGL(k_encode_i64<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, x, count, P, neg, exp);
+  const unsigned grid = lane_grid(c, count, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_encode_i64<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, x, count, P, neg,
+                       exp);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2263,13 +1881,11 @@ fphe_status fphe_decode_i64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_decode_i64<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_decode_i64<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else
-    hipLaunchKernelGGL(k_decode_i64<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
+  const unsigned grid = lane_grid(c, count, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_decode_i64<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count,
+                       out, err);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2280,13 +1896,11 @@ fphe_status fphe_decode_i32(const fphe_ctx* c, const uint32_t* P, uint32_t lp, c
   if (count == 0) return FPHE_OK;
   if (!P || !exp || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((count + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_decode_i32<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_decode_i32<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
-  else
-    hipLaunchKernelGGL(k_decode_i32<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count, out, err);
+  const unsigned grid = lane_grid(c, count, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_decode_i32<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c->K, P, lp, exp, count,
+                       out, err);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2299,15 +1913,10 @@ fphe_status fphe_pack_f64(const fphe_ctx* c, const double* x, size_t count, uint
   DevGuard g(c->device);
   const size_t nout = (count + pack_num - 1) / pack_num;
   const unsigned grid = (unsigned)std::min<size_t>((nout + 63) / 64, (size_t)c->cus * 16);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_pack_f64<128>, dim3(grid), dim3(64), 0, (hipStream_t)stream, x, count, offset_bit, pack_num,
-                       precision, nout, P, neg, exp, err);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_pack_f64<64>, dim3(grid), dim3(64), 0, (hipStream_t)stream, x, count, offset_bit, pack_num,
-                       precision, nout, P, neg, exp, err);
-  else
-    hipLaunchKernelGGL(k_pack_f64<32>, dim3(grid), dim3(64), 0, (hipStream_t)stream, x, count, offset_bit, pack_num,
-                       precision, nout, P, neg, exp, err);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_pack_f64<L() / 2>, dim3(grid), dim3(64), 0, (hipStream_t)stream, x, count, offset_bit,
+                       pack_num, precision, nout, P, neg, exp, err);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2317,16 +1926,11 @@ fphe_status fphe_unpack_f64(const fphe_ctx* c, const uint32_t* P, uint32_t lp, s
   if (npacked == 0 || total == 0) return FPHE_OK;
   if (!P || !out || lp == 0) return FPHE_ERR_ARG;
   DevGuard g(c->device);
-  const unsigned grid = (unsigned)std::min<size_t>((npacked + 255) / 256, (size_t)c->cus * 8);
-  if (c->L1 == 128)
-    hipLaunchKernelGGL(k_unpack_f64<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, P, lp, npacked, offset_bit,
-                       pack_num, precision, total, out);
-  else if (c->L1 == 64)
-    hipLaunchKernelGGL(k_unpack_f64<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, P, lp, npacked, offset_bit,
-                       pack_num, precision, total, out);
-  else
-    hipLaunchKernelGGL(k_unpack_f64<32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, P, lp, npacked, offset_bit,
-                       pack_num, precision, total, out);
+  const unsigned grid = lane_grid(c, npacked, 8);
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_unpack_f64<L() / 2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, P, lp, npacked,
+                       offset_bit, pack_num, precision, total, out);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2341,11 +1945,9 @@ fphe_status fphe_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, const uint
   if (obf && !r && !rng_key) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_encrypt27<256>(c, P, lp, neg, count, obf, r, rng_key, nonce, C, sign, (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_encrypt27<128>(c, P, lp, neg, count, obf, r, rng_key, nonce, C, sign, (hipStream_t)stream);
-  return launch_encrypt27<64>(c, P, lp, neg, count, obf, r, rng_key, nonce, C, sign, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_encrypt27<L()>(c, P, lp, neg, count, obf, r, rng_key, nonce, C, sign, (hipStream_t)stream);
+  });
 }
 
 
@@ -2361,11 +1963,9 @@ fphe_status fphe_encrypt_crt(fphe_ctx* c, const uint32_t* P, uint32_t lp, const 
   if (!r && !rng_key) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_encrypt_crt27<256>(c, P, lp, neg, count, r, rng_key, nonce, C, sign, (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_encrypt_crt27<128>(c, P, lp, neg, count, r, rng_key, nonce, C, sign, (hipStream_t)stream);
-  return launch_encrypt_crt27<64>(c, P, lp, neg, count, r, rng_key, nonce, C, sign, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_encrypt_crt27<L()>(c, P, lp, neg, count, r, rng_key, nonce, C, sign, (hipStream_t)stream);
+  });
 }
 
 
@@ -2378,11 +1978,9 @@ fphe_status fphe_fold(fphe_ctx* c, const uint32_t* Src, const uint8_t* ssign, co
   if (nchunks >= (1ull << 32)) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_fold27<256>(c, Src, ssign, sexp, ord, cstart, clen, nchunks, Co, so, eo, (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_fold27<128>(c, Src, ssign, sexp, ord, cstart, clen, nchunks, Co, so, eo, (hipStream_t)stream);
-  return launch_fold27<64>(c, Src, ssign, sexp, ord, cstart, clen, nchunks, Co, so, eo, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_fold27<L()>(c, Src, ssign, sexp, ord, cstart, clen, nchunks, Co, so, eo, (hipStream_t)stream);
+  });
 }
 
 
@@ -2396,14 +1994,10 @@ fphe_status fphe_fold_segments(fphe_ctx* c, const uint32_t* Src, const uint8_t* 
   if (nterms && !idx && nsrc < nterms) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_fold_segments<256>(c, Src, ssign, sexp, nsrc, idx, seg, nterms, nseg, Co, so, eo, present, err,
+  return with_limbs(c, [&](auto L) {
+    return launch_fold_segments<L()>(c, Src, ssign, sexp, nsrc, idx, seg, nterms, nseg, Co, so, eo, present, err,
                                      (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_fold_segments<128>(c, Src, ssign, sexp, nsrc, idx, seg, nterms, nseg, Co, so, eo, present, err,
-                                     (hipStream_t)stream);
-  return launch_fold_segments<64>(c, Src, ssign, sexp, nsrc, idx, seg, nterms, nseg, Co, so, eo, present, err,
-                                  (hipStream_t)stream);
+  });
 }
 
 
@@ -2438,9 +2032,7 @@ fphe_status fphe_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t*
   if (!C || !P) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256) return launch_decrypt27<256>(c, C, count, P, (hipStream_t)stream);
-  if (c->L2 == 128) return launch_decrypt27<128>(c, C, count, P, (hipStream_t)stream);
-  return launch_decrypt27<64>(c, C, count, P, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) { return launch_decrypt27<L()>(c, C, count, P, (hipStream_t)stream); });
 }
 
 
@@ -2453,11 +2045,9 @@ fphe_status fphe_add_ordered(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa,
   if (!Ca || !sa || !ea || !Cb || !sb || !eb || !Co || !so || !eo) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_add27<256>(c, Ca, sa, ea, Cb, sb, eb, b_stride, count, order, Co, so, eo, err, (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_add27<128>(c, Ca, sa, ea, Cb, sb, eb, b_stride, count, order, Co, so, eo, err, (hipStream_t)stream);
-  return launch_add27<64>(c, Ca, sa, ea, Cb, sb, eb, b_stride, count, order, Co, so, eo, err, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_add27<L()>(c, Ca, sa, ea, Cb, sb, eb, b_stride, count, order, Co, so, eo, err, (hipStream_t)stream);
+  });
 }
 
 fphe_status fphe_add_order(const int32_t* ea, const int32_t* eb, size_t count, uint32_t L2, int32_t* order,
@@ -2495,24 +2085,16 @@ fphe_status fphe_neg(fphe_ctx* c, const uint32_t* Ca, size_t count, uint32_t* Co
   if (!Ca || !Co) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
+  hipStream_t s = (hipStream_t)stream;
   // large vectors: one inverse per group of 16 (8 at 1024 bits) elements (Montgomery's trick)
-  if (count >= binv_min()) {
-    const size_t w = c->L2 == 256 ? binv_scratch_bytes<256>(count)
-                     : c->L2 == 128 ? binv_scratch_bytes<128>(count) : binv_scratch_bytes<64>(count);
-    if (ensure_scratch(c, w, (hipStream_t)stream) != FPHE_OK) return FPHE_ERR_HIP;
-    if (c->L2 == 256)
-      launch_binv27<256>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
-    else if (c->L2 == 128)
-      launch_binv27<128>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
-    else
-      launch_binv27<64>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
-    return hip_ok(hipGetLastError());
-  }
-  const size_t xbytes = (size_t)ntiles_of(count) * c->L1 * FPHE_WAVE * 4;
-  if (ensure_scratch(c, xbytes, (hipStream_t)stream) != FPHE_OK) return FPHE_ERR_HIP;
-  if (c->L2 == 256) launch_inv27<256>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
-  else if (c->L2 == 128) launch_inv27<128>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
-  else launch_inv27<64>(c, Ca, count, nullptr, Co, err, c->scratch, (hipStream_t)stream);
+  if (count >= binv_min())
+    return with_limbs(c, [&](auto L) {
+      if (ensure_scratch(c, binv_scratch_bytes<L()>(count), s) != FPHE_OK) return FPHE_ERR_HIP;
+      launch_binv27<L()>(c, Ca, count, nullptr, Co, err, c->scratch, s);
+      return hip_ok(hipGetLastError());
+    });
+  if (ensure_scratch(c, tile_bytes(count, c->L1), s) != FPHE_OK) return FPHE_ERR_HIP;
+  with_limbs(c, [&](auto L) { launch_inv27<L()>(c, Ca, count, nullptr, Co, err, c->scratch, s); });
   return hip_ok(hipGetLastError());
 }
 
@@ -2524,9 +2106,9 @@ fphe_status fphe_sqmul(fphe_ctx* c, const uint32_t* Ca, const uint32_t* Cb, cons
   if (!Ca || !Cb || !sb || !Co || !so || nsq > (1u << 20)) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256) return launch_sqmul27<256>(c, Ca, Cb, sb, (int)nsq, count, Co, so, (hipStream_t)stream);
-  if (c->L2 == 128) return launch_sqmul27<128>(c, Ca, Cb, sb, (int)nsq, count, Co, so, (hipStream_t)stream);
-  return launch_sqmul27<64>(c, Ca, Cb, sb, (int)nsq, count, Co, so, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_sqmul27<L()>(c, Ca, Cb, sb, (int)nsq, count, Co, so, (hipStream_t)stream);
+  });
 }
 
 
@@ -2542,15 +2124,10 @@ fphe_status fphe_pack_squeeze(fphe_ctx* c, const uint32_t* C, const uint8_t* sig
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
   hipStream_t s = (hipStream_t)stream;
-  if (c->L2 == 256)
-    hipLaunchKernelGGL(k_squeeze_wide<256>, dim3((unsigned)nch), dim3(64), 0, s, c->K, C, sign, count, (int)pack_num,
+  with_limbs(c, [&](auto L) {
+    hipLaunchKernelGGL(k_squeeze_wide<L()>, dim3((unsigned)nch), dim3(64), 0, s, c->K, C, sign, count, (int)pack_num,
                        (int)shift_bit, Co, so);
-  else if (c->L2 == 128)
-    hipLaunchKernelGGL(k_squeeze_wide<128>, dim3((unsigned)nch), dim3(64), 0, s, c->K, C, sign, count, (int)pack_num,
-                       (int)shift_bit, Co, so);
-  else
-    hipLaunchKernelGGL(k_squeeze_wide<64>, dim3((unsigned)nch), dim3(64), 0, s, c->K, C, sign, count, (int)pack_num,
-                       (int)shift_bit, Co, so);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -2561,9 +2138,9 @@ fphe_status fphe_align(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, const
   if (!Ca || !sa || !gap || !Co || !so) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256) return launch_align27<256>(c, Ca, sa, gap, count, Co, so, (hipStream_t)stream);
-  if (c->L2 == 128) return launch_align27<128>(c, Ca, sa, gap, count, Co, so, (hipStream_t)stream);
-  return launch_align27<64>(c, Ca, sa, gap, count, Co, so, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_align27<L()>(c, Ca, sa, gap, count, Co, so, (hipStream_t)stream);
+  });
 }
 
 
@@ -2576,11 +2153,9 @@ fphe_status fphe_mul(fphe_ctx* c, const uint32_t* Ca, const uint8_t* sa, const i
   if (c->ou && lp > (uint32_t)c->L1) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 256)
-    return launch_mul27<256>(c, Ca, sa, ea, P, lp, pneg, pexp, p_stride, count, Co, so, eo, err, (hipStream_t)stream);
-  if (c->L2 == 128)
-    return launch_mul27<128>(c, Ca, sa, ea, P, lp, pneg, pexp, p_stride, count, Co, so, eo, err, (hipStream_t)stream);
-  return launch_mul27<64>(c, Ca, sa, ea, P, lp, pneg, pexp, p_stride, count, Co, so, eo, err, (hipStream_t)stream);
+  return with_limbs(c, [&](auto L) {
+    return launch_mul27<L()>(c, Ca, sa, ea, P, lp, pneg, pexp, p_stride, count, Co, so, eo, err, (hipStream_t)stream);
+  });
 }
 
 fphe_status fphe_chacha20_blocks(const uint32_t key[8], uint32_t counter, const uint32_t nonce[3], size_t nblocks,
@@ -2588,8 +2163,7 @@ fphe_status fphe_chacha20_blocks(const uint32_t key[8], uint32_t counter, const 
   StreamDevGuard sdg(stream);
   if (!key || !nonce || (nblocks && !out)) return FPHE_ERR_ARG;
   if (nblocks == 0) return FPHE_OK;
-  ChaChaKey ck;
-  for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
+  const ChaChaKey ck = chacha_key(key);
   const unsigned grid = (unsigned)std::min<size_t>((nblocks + 255) / 256, 1024);
   hipLaunchKernelGGL(k_chacha_blocks, dim3(grid), dim3(256), 0, (hipStream_t)stream, ck, counter, nonce[0], nonce[1],
                      nonce[2], nblocks, out);
@@ -2633,9 +2207,8 @@ fphe_status fphe_export_signed(fphe_ctx* c, const uint32_t* C, const uint8_t* si
   for (size_t e0 = 0; e0 < count; e0 += span) {
     const size_t m = count - e0 < span ? count - e0 : span;
     const uint32_t* Cs = C + (e0 / FPHE_WAVE) * c->L2 * FPHE_WAVE;
-    fphe_status st = c->L2 == 256   ? launch_mont_const27<256>(c, Cs, m, nullptr, plain, s)
-                     : c->L2 == 128 ? launch_mont_const27<128>(c, Cs, m, nullptr, plain, s)
-                                    : launch_mont_const27<64>(c, Cs, m, nullptr, plain, s);
+    const fphe_status st =
+        with_limbs(c, [&](auto L) { return launch_mont_const27<L()>(c, Cs, m, nullptr, plain, s); });
     if (st != FPHE_OK) return st;
     hipLaunchKernelGGL(k_export_signed, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, c->K.N2, (u32)c->L2,
                        plain, sign + e0, m, mag + e0 * c->L2, neg + e0);
@@ -2655,9 +2228,7 @@ fphe_status fphe_import_signed(fphe_ctx* c, const uint32_t* mag, const uint8_t* 
   hipLaunchKernelGGL(k_import_signed, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, c->K.N2, (u32)c->L2, mag,
                      neg, count, C, sign);
   // into the Montgomery-resident form, in place
-  return c->L2 == 256   ? launch_mont_const27<256>(c, C, count, c->K.N2R2_27, C, s)
-         : c->L2 == 128 ? launch_mont_const27<128>(c, C, count, c->K.N2R2_27, C, s)
-                        : launch_mont_const27<64>(c, C, count, c->K.N2R2_27, C, s);
+  return with_limbs(c, [&](auto L) { return launch_mont_const27<L()>(c, C, count, c->K.N2R2_27, C, s); });
 }
 
 fphe_status fphe_ctx_mont_one(const fphe_ctx* c, uint32_t* one) {
@@ -2737,24 +2308,6 @@ fphe_status fphe_wire_decode(const uint8_t* buf, const int64_t* dig_off, const i
   return hip_ok(hipGetLastError());
 }
 
-// Shader-clock stamps (diagnostics; bench.py's per-leg clock).  `blocks`
-// one-wave workgroups; lane 0 of block b writes {its CU's place -- XCC id << 16 | the SE, SH
-// and CU fields of HW_ID --, the shader-clock counter (clock64: s_memtime, counts SCLK
-// cycles), the constant-rate counter (wall_clock64)} to out[3b .. 3b+2] with vector stores.
-// The shader-clock counters of different CUs are not synchronised (a before/after pair from
-// two CUs of one XCD can even run backwards), so the host pairs two stamps queued around a
-// launch by CU; with a few thousand blocks every CU is stamped on both sides.
-__global__ __launch_bounds__(64) void k_clock_stamp(unsigned long long* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  const unsigned long long c = clock64();
-  const unsigned long long w = wall_clock64();
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15u;   // HW_REG_XCC_ID
-  const unsigned hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4) & 255u;    // HW_ID[15:8]
-  out[3 * blockIdx.x] = (xcc << 16) | hw;
-  out[3 * blockIdx.x + 1] = c;
-  out[3 * blockIdx.x + 2] = w;
-}
-
 fphe_status fphe_clock_stamp(uint64_t* out, uint32_t blocks, uint32_t* wall_khz, void* stream) {
   StreamDevGuard sdg(stream);
   if (!out || blocks == 0 || blocks > 65536) return FPHE_ERR_ARG;
@@ -2769,265 +2322,6 @@ fphe_status fphe_clock_stamp(uint64_t* out, uint32_t blocks, uint32_t* wall_khz,
   return hip_ok(hipGetLastError());
 }
 
-}  // extern "C"
-
-// ======================================================================================
-// Okamoto-Uchiyama (rust/fate_utils/crates/ou/src/lib.rs:69-138): context, encrypt, decrypt.
-// Every other entry point reaches an OU context through the N2* slots of KeyArgs, which hold
-// n = p^2 q.
-// ======================================================================================
-namespace {
-
-// Host Montgomery products (32-bit CIOS, R = 2^(32 L)) for the setup work hbn::mod is too slow
-// for: g^(p-1) mod p^2 and the ~10^4 products of the fixed-base tables.
-struct HostMont {
-  Limbs N, R2;
-  size_t L;
-  u32 n0;
-  HostMont(const Limbs& n, size_t l) : N(hbn::padded(n, l)), R2(hbn::padded(hbn::pow2_mod(64 * l, n), l)), L(l),
-                                       n0(hbn::neg_inv32(n[0])) {}
-  // a b R^-1 mod N for a, b < N (L words each)
-  Limbs mul(const Limbs& a, const Limbs& b) const {
-    std::vector<u32> t(L + 2, 0u);
-    for (size_t i = 0; i < L; ++i) {
-      u64 c = 0;
-      for (size_t j = 0; j < L; ++j) {
-        const u64 s = (u64)a[j] * b[i] + t[j] + c;
-        t[j] = (u32)s;
-        c = s >> 32;
-      }
-      u64 s = (u64)t[L] + c;
-      t[L] = (u32)s;
-      t[L + 1] = (u32)(s >> 32);
-      const u32 m = t[0] * n0;
-      c = ((u64)m * N[0] + t[0]) >> 32;
-      for (size_t j = 1; j < L; ++j) {
-        s = (u64)m * N[j] + t[j] + c;
-        t[j - 1] = (u32)s;
-        c = s >> 32;
-      }
-      s = (u64)t[L] + c;
-      t[L - 1] = (u32)s;
-      t[L] = t[L + 1] + (u32)(s >> 32);
-    }
-    // t < 2N: one conditional subtraction, in place
-    bool ge = t[L] != 0;
-    if (!ge) {
-      ge = true;  // t == N counts
-      for (size_t j = L; j-- > 0;)
-        if (t[j] != N[j]) { ge = t[j] > N[j]; break; }
-    }
-    if (ge) {
-      u64 br = 0;
-      for (size_t j = 0; j < L; ++j) {
-        const u64 d = (u64)t[j] - N[j] - br;
-        t[j] = (u32)d;
-        br = d >> 63;
-      }
-    }
-    t.resize(L);
-    return t;
-  }
-  Limbs to(const Limbs& x) const { return mul(hbn::padded(x, L), R2); }  // x R
-  Limbs from(const Limbs& X) const {                                       // X R^-1
-    Limbs one(L, 0u);
-    one[0] = 1;
-    return mul(X, one);
-  }
-  // x^e mod N (plain in, plain out), x < N
-  Limbs pow(const Limbs& x, const Limbs& e) const {
-    const Limbs X = to(x);
-    Limbs A = to(Limbs{1});
-    for (size_t i = hbn::bitlen(e); i-- > 0;) {
-      A = mul(A, A);
-      if (hbn::bit(e, i)) A = mul(A, X);
-    }
-    return hbn::norm(from(A));
-  }
-};
-
-// rows of the fixed-base table (ou_dev.h) for one base: M(base^(d 2^(W i))) for i < nwin,
-// d = 1 .. 2^W - 1, as NL limbs of LB bits, appended to `out`.  Reng = 2^(LB NL) mod n.
-void ou_table_rows(const HostMont& M, const Limbs& base, u32 nwin, const Limbs& Reng, int NL, int LB,
-                   std::vector<u32>& out) {
-  constexpr u32 D = (1u << kOuWin) - 1u;
-  Limbs b = M.to(base);  // base^(2^(W i)) in the host's Montgomery form
-  for (u32 i = 0; i < nwin; ++i) {
-    Limbs e = b;
-    for (u32 d = 1; d <= D; ++d) {
-      const Limbs row = to_radix(hbn::norm(M.mul(e, Reng)), NL, LB);  // (x R32)(R_eng) / R32 = x R_eng
-      out.insert(out.end(), row.begin(), row.end());
-      e = M.mul(e, b);
-    }
-    b = e;  // base^(2^W 2^(W i))
-  }
-}
-
-template <int L>
-fphe_status launch_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
-                              const uint32_t key[8], uint64_t nonce, uint32_t* C, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI;
-  auto kern = OU<TPI>::template encrypt<L, kOuWin>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const size_t span = span_elems(c, kern, lds, E);
-  const size_t m0 = count < span ? count : span;
-  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "ou_encrypt27");
-  const size_t rbytes = (size_t)ntiles_of(m0) * L * FPHE_WAVE * 4;
-  ChaChaKey ck;
-  if (!r) {
-    for (int i = 0; i < 8; ++i) ck.k[i] = key[i];
-    if (ensure_scratch(c, rbytes, s) != FPHE_OK) return FPHE_ERR_HIP;
-  }
-  for (size_t e0 = 0; e0 < count; e0 += span) {  // spans run in stream order over one scratch
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
-    const u32* rbuf = r ? r + t0 * L * FPHE_WAVE : nullptr;
-    if (!r) {  // draw_r over the L words of n (K.nm1, K.nbits of an OU context)
-      const unsigned rgrid = (unsigned)std::min<size_t>((m + 255) / 256, (size_t)c->cus * 4);
-      hipLaunchKernelGGL(k_draw_r<L>, dim3(rgrid), dim3(256), 0, s, c->K, m, ck, nonce, e0, c->scratch);
-      rbuf = c->scratch;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, c->ou_tab, c->ou_hwin, P + t0 * lp * FPHE_WAVE, lp,
-                       rbuf, m, C + t0 * L * FPHE_WAVE, (u32)NL);
-    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
-}
-
-template <int L>
-fphe_status launch_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, hipStream_t s) {
-  constexpr int TPI = L / 32, E = FPHE_WAVE / TPI, NL = rad_ll(TPI) * TPI, LQ = L / 2;
-  auto kern = OU<TPI>::template decrypt<L, kWinSlide>();
-  const size_t lds = (size_t)kWavesPerBlock * NL * E * 4;
-  set_lds(kern, lds);
-  const size_t span = span_elems(c, kern, lds, E);
-  const size_t m0 = count < span ? count : span;
-  const unsigned grid = occ_grid(c, kern, lds, (m0 + E - 1) / E, "ou_decrypt27");
-  const size_t tbytes = (size_t)grid * kWavesPerBlock * kTabEntries<kWinSlide> * rad_ll(TPI) * FPHE_WAVE * 4;
-  const size_t ybytes = (size_t)ntiles_of(m0) * L * FPHE_WAVE * 4;
-  if (ensure_scratch(c, tbytes + ybytes, s) != FPHE_OK) return FPHE_ERR_HIP;
-  u32* Y = c->scratch + tbytes / 4;
-  auto ktail = k_ou_decrypt_tail<L>;
-  const size_t lds2 = (size_t)kWavesPerBlock * LQ * FPHE_WAVE * 4;
-  set_lds(ktail, lds2);
-  for (size_t e0 = 0; e0 < count; e0 += span) {
-    const size_t m = count - e0 < span ? count - e0 : span, t0 = e0 / FPHE_WAVE;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, s, c->K, C + t0 * L * FPHE_WAVE, m, Y, c->scratch, (u32)NL);
-    hipLaunchKernelGGL(ktail, dim3(grid_for(c, m, bpc_for_slot(LQ))), dim3(kBlock), lds2, s, c->K, (const u32*)Y,
-                       ntiles_of(m), P + t0 * LQ * FPHE_WAVE);
-    if (hipGetLastError() != hipSuccess) return FPHE_ERR_HIP;
-  }
-  return FPHE_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-fphe_status fphe_ou_ctx_create(int device, uint32_t key_bits, const uint32_t* n_w, const uint32_t* g_w,
-                               const uint32_t* h_w, const uint32_t* p_w, const uint32_t* q_w, fphe_ctx** out) {
-  if (!out || !n_w || !g_w || !h_w) return FPHE_ERR_ARG;
-  if (key_bits < 1024 || key_bits > 4096 || key_bits % 2) return FPHE_ERR_ARG;
-  if ((p_w == nullptr) != (q_w == nullptr)) return FPHE_ERR_ARG;
-  const int L2 = key_bits <= 2048 ? 64 : 128, L1 = L2 / 2;
-  try {
-    const Limbs n = from_words(n_w, L2), g = from_words(g_w, L2), h = from_words(h_w, L2);
-    if (n.empty() || !(n[0] & 1)) return FPHE_ERR_KEY;
-    if (hbn::bitlen(n) != key_bits) return FPHE_ERR_KEY;  // ou/src/lib.rs:80 keeps bits(n) == bit_length
-    if (g.empty() || h.empty() || hbn::cmp(g, n) >= 0 || hbn::cmp(h, n) >= 0) return FPHE_ERR_KEY;
-    std::vector<u32> blob;
-    auto put = [&](const Limbs& v, size_t len) -> size_t {
-      const size_t off = blob.size();
-      Limbs p = hbn::padded(v, len);
-      blob.insert(blob.end(), p.begin(), p.end());
-      while (blob.size() % 4) blob.push_back(0);  // 16-byte aligned sections
-      return off;
-    };
-    const int TPI2 = L2 / 32, LB2 = rad_lb(TPI2), NL2 = rad_ll(TPI2) * TPI2;
-    const Limbs Reng = hbn::pow2_mod((size_t)LB2 * NL2, n);
-    const size_t o_N2 = put(n, L2);
-    const size_t o_n = put(n, L2 + 1);
-    const size_t o_nm1 = put(hbn::sub(n, Limbs{1}), L2);
-    const size_t o_N2_27 = put(to_radix(n, NL2, LB2), NL2);
-    const size_t o_N2R1_27 = put(to_radix(Reng, NL2, LB2), NL2);
-    const size_t o_N2R2_27 = put(to_radix(hbn::pow2_mod((size_t)2 * LB2 * NL2, n), NL2, LB2), NL2);
-    const size_t o_N2R3_27 = put(to_radix(hbn::pow2_mod((size_t)3 * LB2 * NL2, n), NL2, LB2), NL2);
-    const size_t o_N2M1 = put(Reng, L2);
-    size_t o_P2_27 = 0, o_P2R1_27 = 0, o_pm1 = 0, o_p = 0, o_pinv2 = 0, o_hpR = 0;
-    u32 p2n0 = 0, pn0 = 0;
-    int pm1b = 0, pb = 0;
-    const bool has_sk = p_w != nullptr;
-    if (has_sk) {
-      const Limbs p = from_words(p_w, L1), q = from_words(q_w, L1);
-      if (p.empty() || q.empty() || !(p[0] & 1) || !(q[0] & 1)) return FPHE_ERR_KEY;
-      if (hbn::cmp(p, q) == 0) return FPHE_ERR_KEY;
-      const Limbs P2 = hbn::mul(p, p);
-      if (hbn::cmp(hbn::mul(P2, q), n) != 0) return FPHE_ERR_KEY;
-      const Limbs pm1 = hbn::sub(p, Limbs{1});
-      // h_p = L(g^(p-1) mod p^2)^-1 mod p, L(x) = (x - 1) / p (ou/src/lib.rs:120-131); a g whose
-      // power is 1 has no inverse: inv_mod throws, FPHE_ERR_KEY
-      const HostMont MP(P2, (size_t)L2);
-      const Limbs y = MP.pow(hbn::mod(g, P2), pm1);
-      if (y.empty()) return FPHE_ERR_KEY;
-      const Limbs ym1 = hbn::sub(y, Limbs{1});
-      // exact quotient (y - 1) / p by the inverse of p mod 2^(32 L1), as crt_tail does
-      Limbs Lg = hbn::mul(hbn::padded(ym1, (size_t)L2), hbn::inv_pow2(p, (size_t)L1));
-      Lg.resize((size_t)L1, 0u);
-      const Limbs hp = hbn::inv_mod(hbn::norm(Lg), p);
-      o_P2_27 = put(to_radix(P2, NL2, LB2), NL2);
-      o_P2R1_27 = put(to_radix(hbn::pow2_mod((size_t)LB2 * NL2, P2), NL2, LB2), NL2);
-      o_pm1 = put(pm1, L1 + 1);
-      o_p = put(p, L1);
-      o_pinv2 = put(hbn::inv_pow2(p, (size_t)L1), L1);
-      o_hpR = put(hbn::mod(hbn::mul(hp, hbn::pow2_mod((size_t)32 * L1, p)), p), L1);
-      p2n0 = hbn::neg_inv32(P2[0]);
-      pn0 = hbn::neg_inv32(p[0]);
-      pm1b = (int)hbn::bitlen(pm1);
-      pb = (int)hbn::bitlen(p);
-    }
-    // fixed-base tables (ou_dev.h): row 0 = M(1), then h's windows over bits(n), then g's over
-    // the L1 plaintext words a call may pass
-    const u32 hwin = (key_bits + kOuWin - 1) / kOuWin, gwin = (u32)L1 * 32u / kOuWin;
-    while (blob.size() % 64) blob.push_back(0);
-    const size_t o_tab = blob.size();
-    {
-      const HostMont MN(n, (size_t)L2);
-      const Limbs RengP = hbn::padded(Reng, (size_t)L2);
-      const Limbs one = to_radix(Reng, NL2, LB2);
-      blob.reserve(blob.size() + (size_t)(1 + ((1u << kOuWin) - 1u) * (hwin + gwin)) * NL2);
-      blob.insert(blob.end(), one.begin(), one.end());
-      ou_table_rows(MN, h, hwin, RengP, NL2, LB2, blob);
-      ou_table_rows(MN, g, gwin, RengP, NL2, LB2, blob);
-    }
-    auto* c = new fphe_ctx();
-    c->device = device; c->key_bits = key_bits; c->L1 = L1; c->L2 = L2; c->LQ = L1 / 2; c->has_sk = has_sk;
-    c->ou = true;
-    c->ou_hwin = hwin;
-    // (the wide_* path options are stored and read back but select nothing on an OU context)
-    DevGuard dg(device);
-    if (ctx_device_init(c, device, blob) != FPHE_OK) { delete c; return FPHE_ERR_HIP; }
-    u32* b = c->blob;
-    KeyArgs& K = c->K;
-    K.N2 = b + o_N2; K.n = b + o_n; K.nm1 = b + o_nm1;
-    K.n2_n0inv = hbn::neg_inv32(n[0]);
-    K.nbits = (int)key_bits;
-    K.N2_27 = b + o_N2_27; K.N2R1_27 = b + o_N2R1_27; K.N2R2_27 = b + o_N2R2_27; K.N2R3_27 = b + o_N2R3_27;
-    K.n2_np27 = K.n2_n0inv & ((1u << LB2) - 1u);
-    K.N2M1 = b + o_N2M1;
-    K.nn_inv27 = (0u - K.n2_n0inv) & ((1u << LB2) - 1u);  // n^-1 mod 2^LB, k_ou_inv27's safegcd
-    if (has_sk) {
-      K.P2_27 = b + o_P2_27; K.P2R1_27 = b + o_P2R1_27; K.p2_np27 = p2n0 & ((1u << LB2) - 1u);
-      K.pm1 = b + o_pm1; K.pm1_bits = pm1b; K.p = b + o_p; K.p_bits = pb; K.p_n0inv = pn0;
-      K.pinv2 = b + o_pinv2; K.hpR = b + o_hpR;
-    }
-    c->ou_tab = b + o_tab;
-    *out = c;
-    return FPHE_OK;
-  } catch (...) {
-    return FPHE_ERR_KEY;
-  }
-}
-
 fphe_status fphe_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t count, const uint32_t* r,
                             const uint32_t rng_key[8], uint64_t nonce, uint32_t* C, void* stream) {
   if (!c || !c->ou) return FPHE_ERR_ARG;
@@ -3037,8 +2331,9 @@ fphe_status fphe_ou_encrypt(fphe_ctx* c, const uint32_t* P, uint32_t lp, size_t 
   if (!r && !rng_key) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 128) return launch_ou_encrypt<128>(c, P, lp, count, r, rng_key, nonce, C, (hipStream_t)stream);
-  return launch_ou_encrypt<64>(c, P, lp, count, r, rng_key, nonce, C, (hipStream_t)stream);
+  return with_limbs<128>(c, [&](auto L) {
+    return launch_ou_encrypt<L()>(c, P, lp, count, r, rng_key, nonce, C, (hipStream_t)stream);
+  });
 }
 
 fphe_status fphe_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32_t* P, void* stream) {
@@ -3048,8 +2343,7 @@ fphe_status fphe_ou_decrypt(fphe_ctx* c, const uint32_t* C, size_t count, uint32
   if (!C || !P) return FPHE_ERR_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DevGuard g(c->device);
-  if (c->L2 == 128) return launch_ou_decrypt<128>(c, C, count, P, (hipStream_t)stream);
-  return launch_ou_decrypt<64>(c, C, count, P, (hipStream_t)stream);
+  return with_limbs<128>(c, [&](auto L) { return launch_ou_decrypt<L()>(c, C, count, P, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 // kernels27.h instantiates every kernel in both and the launchers pick by TPI (KS<TPI>).
 #pragma once
 #include "mont_dev.h"
+#include "radix.h"  // rad_lb / rad_ll: the engine a TPI runs on (host and device)
 
 #ifndef FPHE_TAB_BATCH
 #define FPHE_TAB_BATCH 1
@@ -85,12 +86,4 @@ constexpr int LL = 37;
 #undef RG_SECTION
 #undef RG_GEN_FILE
 }  // namespace r28
-
-// limb geometry of the engine a TPI runs on (host and device): 28 x 37, or 27 x 38 for the
-// 4096-bit geometry when built with FPHE_RADIX4=27
-#ifndef FPHE_RADIX4
-#define FPHE_RADIX4 28
-#endif
-constexpr int rad_lb(int tpi) { return tpi == 4 ? FPHE_RADIX4 : 28; }
-constexpr int rad_ll(int tpi) { return rad_lb(tpi) == 27 ? 38 : 37; }
 }  // namespace fphe

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 KEYS = ou_ref.load_keys()
 BITS = sorted(KEYS)
 COUNT = 67
-W = 4  # kOuWin (fate_amd/csrc/fate_phe.hip)
+W = 4  # kOuWin (fate_amd/csrc/key_blob.h)
 RNG_KEY = [0x01234567, 0x89ABCDEF, 0xDEADBEEF, 0x0BADF00D, 0x13579BDF, 0x2468ACE0, 0xFEEDFACE, 0x31415926]
 NONCE = (0x5EED << 40) ^ 0xC0FFEE
 
