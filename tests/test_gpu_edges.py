@@ -393,36 +393,57 @@ def test_unsupported_key_sizes_decline():
         P.keygen(1023)
 
 
-@pytest.mark.parametrize("bits", [1024, 2048])
-def test_extreme_operands(bits):
-    """Operands at the edges of the 28-bit engine's bounds (all-ones limbs, n^2 - 1, 2^k - 1
-    just under n^2, 2, the literal 1) through ct-add with exponent gaps, ct x pt by small,
-    big (n - small: a full-size exponent) and negative plaintexts, neg, the exponent
-    alignment and decrypt; obfuscated encryption with r = 1 and r = n - 1 of the largest and
-    smallest encodable significands.  Bit-exact against the oracle."""
-    p, q, sk, pk, coder, osk, opk = load(bits)
+def run_extreme_operands(p, q, count=None):
+    """The body of test_extreme_operands for the key (p, q); tests/test_gpu_extreme_moduli.py runs
+    it on the keys whose moduli are themselves extreme.  The operands are the canonical edge values
+    below and, so that all-ones limbs reach the kernels as such, the canonical values whose
+    resident form M(c) = c R mod n^2 is an edge pattern (tests/extreme_ref.py; the canonical
+    n^2 - 1 is stored as a random-looking M(.)).  count: keep that many operands (the widest
+    keys, where the Python reference is the slow side), resident patterns first."""
+    from tests import extreme_ref as X
+    sk, pk, coder = P.keypair_from_primes(p, q)
+    osk, opk = O.keypair_from_primes(p, q)
     ns, n = opk.ns, opk.n
     L = ns.bit_length()
     m28 = (L - 1) // 28
     vals = [2, ns - 1, ns - 2, (ns - 1) // 2, (1 << (L - 1)) - 1, (1 << (28 * m28)) - 1,
             ns - (1 << (28 * (m28 - 1))), int("5" * (L // 4 - 1), 16) % ns, 1]
-    signs = [0, 1, 0, 1, 0, 0, 1, 0, 0]
-    cts = [O.Ciphertext(-(ns - v) if s else v, e) for v, s, e in zip(vals, signs, [0, -3, 2, 0, -1, 0, 5, -2, 0])]
-    other = [O.Ciphertext(v, e) for v, e in zip(reversed(vals), [1, 0, -3, 4, 0, -1, 0, 0, 3])]
+    base = len(vals)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = X.resident_patterns(ns, pk._key.L2)
+    extra = X.units(X.canonical(res, X.mont_r(pk._key, dev), ns), ns)  # neg below needs units
+    assert len(extra) == len(res)  # a pattern is a multiple of p or q for no committed key
+    vals = vals + extra
+    if count is not None:
+        vals = (extra + vals[:base])[:count]
+    nv = len(vals)
+
+    def cyc(xs):
+        return [xs[i % len(xs)] for i in range(nv)]
+
+    signs = cyc([0, 1, 0, 1, 0, 0, 1, 0, 0])
+    cts = [O.Ciphertext(-(ns - v) if s else v, e) for v, s, e in zip(vals, signs, cyc([0, -3, 2, 0, -1, 0, 5, -2, 0]))]
+    other = [O.Ciphertext(v, e) for v, e in zip(reversed(vals), cyc([1, 0, -3, 4, 0, -1, 0, 0, 3]))]
     dv = P.CiphertextVector.from_signed_ints([c.c for c in cts], [c.exp for c in cts], pk.ns, pk._key.L2)
     dw = P.CiphertextVector.from_signed_ints([c.c for c in other], [c.exp for c in other], pk.ns, pk._key.L2)
+    # the resident patterns arrive on the device as listed
+    if count is None:
+        rows = P.tiles_to_cols(dv.C).t()[base:nv].cpu().numpy().view(np.uint32)
+        stored = [sum(int(w) << (32 * k) for k, w in enumerate(r)) for r in rows]
+        assert all(s_ in res for s_ in stored) and len(set(stored)) == len(extra)
 
     def host(v):
         cs, es = v.to_signed_ints(pk.ns)
         return list(zip(cs, es))
 
+    assert host(dv) == [(c.c, c.exp) for c in cts]
     assert host(dv.add(pk, dw)) == [(c.c, c.exp) for c in (O.ct_add(opk, a, b) for a, b in zip(cts, other))]
     assert host(dv.neg(pk)) == [(c.c, c.exp) for c in (O.ct_neg(opk, a) for a in cts)]
-    pts = [O.Plaintext(v, e) for v, e in zip([3, n - 5, n - 1, n // 2, 1, 0, 7, (1 << 60) + 1, 2],
-                                             [0, 0, 1, -1, 0, 0, 0, -2, 0])]
+    pts = [O.Plaintext(v, e) for v, e in zip(cyc([3, n - 5, n - 1, n // 2, 1, 0, 7, (1 << 60) + 1, 2]),
+                                             cyc([0, 0, 1, -1, 0, 0, 0, -2, 0]))]
     pv = P.PlaintextVector.from_ints([t.significant for t in pts], [t.exp for t in pts])
     assert host(dv.mul(pk, pv)) == [(c.c, c.exp) for c in (O.ct_mul(opk, a, t) for a, t in zip(cts, pts))]
-    gaps = [5, 0, 1, 31, 2, 0, 3, 9, 4]
+    gaps = cyc([5, 0, 1, 31, 2, 0, 3, 9, 4])
     al = P._align(pk, dv, torch.tensor(gaps))
     assert host(al) == [((c.c if g == 0 else pow(c.c % ns, 16 ** g, ns)), c.exp) for c, g in zip(cts, gaps)]
     sig, _ = sk.decrypt_to_encoded(dv).to_ints()
@@ -437,6 +458,18 @@ def test_extreme_operands(bits):
     for k in (pk, pk_pub):  # key-holder CRT path and public-key path
         enc = k.encrypt_encoded(P.PlaintextVector.from_ints(sigs, [0] * len(sigs)), True, r=rs)
         assert host(enc) == [(c.c, c.exp) for c in want]
+
+
+@pytest.mark.parametrize("bits", [1024, 2048])
+def test_extreme_operands(bits):
+    """Operands at the edges of the 28-bit engine's bounds (all-ones limbs, n^2 - 1, 2^k - 1
+    just under n^2, 2, the literal 1, and the values whose resident form is all-ones limbs, one
+    limb zero at a lane seam, alternating limbs) through ct-add with exponent gaps, ct x pt by
+    small, big (n - small: a full-size exponent) and negative plaintexts, neg, the exponent
+    alignment and decrypt; obfuscated encryption with r = 1 and r = n - 1 of the largest and
+    smallest encodable significands.  Bit-exact against the oracle."""
+    p, q = load(bits)[:2]
+    run_extreme_operands(p, q)
 
 
 def _rows(v, idx, pk):
